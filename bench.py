@@ -18,7 +18,13 @@ The headline arithmetic is `bf16x6`: every fp32 operand split into three bf16 pl
 significand bits), six MFMA passes per k-step, fp32 accumulate, fp32 storage -- the reference's fp32
 arithmetic (logits within 1e-6 of the exact-fp32 MFMA chain) on the bf16 matrix cores.
 
-Prints ONE JSON line on rank 0.  At N=1 the same line also carries
+Prints ONE JSON line on rank 0: the headline block (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` = wall milliseconds of one timed step).  A plain run does only that: set-up, warm-up, the
+`--steps` timed steps, the outputs of the last of them if `--dump-outputs DIR` is given, the line.
+
+`--full` adds what the headline figure does not need:
+  * `roofline`: HIP-event sample of the conv launches of every timed block (every 16th iteration);
+At N=1 `--full` also runs
   * `secondary.s32` / `secondary.s32_bf16act`: BASELINE configs[4], 32-frame clips, in the headline
     arithmetic and in its stated form (bf16 activation storage, 2 MFMA passes);
   * `secondary.bf16x3`: the 16-bit-significand split (3 passes; within north_star's 1e-3, not fp32);
@@ -27,6 +33,17 @@ Prints ONE JSON line on rank 0.  At N=1 the same line also carries
   * `cpu_baseline`: the CPU oracle on the host cores (port), plus the
     reference-literal cost line (B=16 forward per iteration + weight gradients);
   * `summary`: the headline figures of every block again, compact, as the LAST key of the line.
+
+`--dump-outputs DIR` writes what the headline block's last timed step returned as DIR/<name>.npy (float32 /
+float64, at most DUMP_BYTES in all): the gathered per-clip records of every rank (clip_id, pred_class, target,
+the four scores, time_mask) and rank 0's init_mask, ranking, snapped and Grad-CAM maps (`gradcam`, or when the
+maps exceed the budget `gradcam_sample`: the elements at DUMP_CAM_ELEMS seeded random flat indices, sorted).
+The clips and weights are a pure function of the arguments, so two builds can be compared output for output.
+
+The headline block's per-layer kernel choice is never picked by timing unless `--tuning FILE` asks for it: it is
+TUNING_FILE (a choice the tuner made on an MI355X for the default plan) when that record fits the plan, the
+built-in choice otherwise.  The 300-step Adam search carries any last-bit difference between kernel variants into
+the masks, scores and rankings, so a choice by timing would make two runs of the same arguments differ.
 """
 import argparse
 import ctypes
@@ -63,6 +80,9 @@ HEADLINE_MATH = "bf16x6"
 NCLASS = 96   # IVF_PROFILE_CLASSES
 GATHER_CAMS = os.environ.get("IVF_BENCH_GATHER_CAMS") == "1"   # also all-gather the Grad-CAM maps (SURVEY 8e's optional payload)
 PMC_FILE = os.path.join(ROOT, "profiles", "r03_pmc_hbm_traffic.json")
+TUNING_FILE = os.path.join(ROOT, "profiles", "r03_bench_tuning.json")   # headline kernel choice (read only)
+DUMP_BYTES = 64_000_000          # --dump-outputs: all files together
+DUMP_CAM_ELEMS = 12_000_000      # Grad-CAM elements kept when the whole maps do not fit beside the rest
 
 
 def parse_args():
@@ -77,10 +97,16 @@ def parse_args():
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary blocks (other arithmetic modes, S32, ConvLSTM)")
     ap.add_argument("--cpu-sample-iters", type=int, default=10)
     ap.add_argument("--tuning", default=None,
-                    help="JSON file with a per-layer kernel choice: loaded instead of autotuning when it exists and fits "
-                         "this plan, written after autotuning otherwise (profiling runs: no tuner launches in the trace)")
+                    help="JSON file with a per-layer kernel choice for the headline block: loaded when it exists and "
+                         "fits this plan, written after autotuning otherwise (default: the committed choice or the "
+                         "built-in one, never autotuned)")
     ap.add_argument("--math", choices=sorted(MODES), default=HEADLINE_MATH,
                     help="arithmetic of the Unit3D convolutions of the headline block")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline sample, the secondary blocks and the CPU baseline (N=1; see "
+                         "--no-secondary / --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the headline block's last timed step to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -261,8 +287,25 @@ def collect_roofline(L, eng, B):
     }
 
 
-def timed_i3d(torch, dist, dev, rank, world, math, B, T, iters, steps, warmup, lam1, lam2, tuning_file=None):
-    """W untimed + K timed steps of the full I3D search.  Returns (elapsed_s, roofline, engine math)."""
+def read_tuning(path, B, math, T, lib_version):
+    """The per-layer kernel choice saved in `path` when it was made for this plan (batch, arithmetic, frames) and
+    this variant table (lib_version: variant ids mean nothing to another table); None otherwise."""
+    try:
+        doc = json.load(open(path))
+        if doc.get("batch") == B and doc.get("math") == math and doc.get("frames") == T and \
+                doc.get("lib_version") == lib_version:
+            return doc["variants"]
+    except (OSError, ValueError, KeyError):
+        pass
+    return None
+
+
+def timed_i3d(torch, dist, dev, rank, world, math, B, T, iters, steps, warmup, lam1, lam2, tuning_file=None,
+              fixed_tuning=None, profile=False):
+    """W untimed + K timed steps of the full I3D search.  Returns (elapsed_s, roofline or None, engine math,
+    (search result dict, gathered records) of the last timed step); profile=True samples the roofline.
+    Kernel choice: `tuning_file` loaded, or autotuned and saved there; else `fixed_tuning` loaded when it fits, the
+    built-in choice when it does not; with neither, autotuned."""
     import ivf_engine
     import ivf_lib as L
     import ivf_recipe as R
@@ -270,23 +313,17 @@ def timed_i3d(torch, dist, dev, rank, world, math, B, T, iters, steps, warmup, l
     import ivf_shard
     eng = ivf_engine.I3DEngine(174, (3, T, 224, 224), max_batch=B, softmax=True,
                                stride_mod_layers="" if T == 16 else "none", device=dev, math=math)
-    saved = None
-    if tuning_file and os.path.exists(tuning_file):
-        try:
-            doc = json.load(open(tuning_file))
-            # (lib_version: the variant ids of a saved choice are only meaningful for the variant table that made them)
-            if doc.get("batch") == B and doc.get("math") == eng.math and doc.get("frames") == T and \
-                    doc.get("lib_version") == L.lib().ivf_version():
-                saved = doc["variants"]
-        except (OSError, ValueError, KeyError):
-            saved = None
-    eng.load_state_dict(R.i3d_state_dict(num_classes=174), autotune=(rank == 0 and saved is None))
+    path = tuning_file or fixed_tuning
+    saved = read_tuning(path, B, eng.math, T, L.lib().ivf_version()) if path else None
+    tune_on_miss = bool(tuning_file) or not fixed_tuning
+    eng.load_state_dict(R.i3d_state_dict(num_classes=174), autotune=(rank == 0 and saved is None and tune_on_miss))
     if saved is not None:
         try:
             eng.set_tuning(saved)
         except L.IvfError:
-            eng.autotune()
             saved = None
+            if tune_on_miss:
+                eng.autotune()
     if tuning_file and saved is None and rank == 0:
         try:
             json.dump({"batch": B, "math": eng.math, "frames": T, "lib_version": L.lib().ivf_version(),
@@ -311,7 +348,7 @@ def timed_i3d(torch, dist, dev, rank, world, math, B, T, iters, steps, warmup, l
     def step(i):
         res = searcher.run(batches[i], labels[i])
         rec = ivf_search.pack_records(clip_ids[i], res, T, with_cam=GATHER_CAMS)   # (maps: 3.2 MB per clip, optional)
-        return ivf_shard.gather_records(rec, equal_shards=True)    # ONE RCCL all_gather when world > 1
+        return res, ivf_shard.gather_records(rec, equal_shards=True)    # ONE RCCL all_gather when world > 1
 
     def fence():
         if dist is not None:
@@ -320,22 +357,55 @@ def timed_i3d(torch, dist, dev, rank, world, math, B, T, iters, steps, warmup, l
 
     for i in range(warmup):
         step(i)
-    # sample conv launches on every 16th iteration with HIP events on the launch stream
-    L.check(L.lib().ivf_profile_enable(16, 200000))
+    if profile:
+        # sample conv launches on every 16th iteration with HIP events on the launch stream
+        L.check(L.lib().ivf_profile_enable(16, 200000))
     fence()
     t0 = time.perf_counter()
     for i in range(warmup, total):
-        step(i)
+        last = step(i)
     fence()
     elapsed = time.perf_counter() - t0
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
-    roof = collect_roofline(L, eng, B) if rank == 0 else None
-    if rank != 0:
+    roof = collect_roofline(L, eng, B) if profile and rank == 0 else None
+    if profile and rank != 0:
         L.check(L.lib().ivf_profile_disable())
-    return elapsed, roof, eng.math
+    return elapsed, roof, eng.math, last
+
+
+def dump_outputs(torch, out_dir, res, rec, T):
+    """--dump-outputs: the arrays the last timed step returned -> out_dir/<name>.npy (see the module docstring)."""
+    import numpy as np
+    import ivf_search
+    arrays = {}
+    ni = len(ivf_search.RECORD_INT_FIELDS)
+    for i, k in enumerate(ivf_search.RECORD_INT_FIELDS):
+        arrays[k] = rec[:, i].double()
+    flt = rec[:, ni:].contiguous().view(torch.float32)
+    nf = len(ivf_search.RECORD_FLOAT_FIELDS)
+    for i, k in enumerate(ivf_search.RECORD_FLOAT_FIELDS):
+        arrays[k] = flt[:, i]
+    arrays["time_mask"] = flt[:, nf:nf + T]
+    arrays["init_mask"] = res["init_mask"].float()
+    arrays["ranking"] = res["ranking"].double()
+    arrays["snapped"] = res["snapped"].float()
+    cam = res["gradcam"].float()
+    rest = sum(a.numel() * a.element_size() for a in arrays.values())
+    if rest + cam.numel() * 4 <= DUMP_BYTES:
+        arrays["gradcam"] = cam
+    else:
+        g = torch.Generator(device="cpu").manual_seed(0)
+        idx = torch.randint(cam.numel(), (DUMP_CAM_ELEMS,), generator=g).sort().values
+        arrays["gradcam_sample"] = cam.reshape(-1)[idx.to(cam.device)]
+    total = sum(a.numel() * a.element_size() for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a.detach().cpu().numpy())
 
 
 def convlstm_block(torch, dev, B=256, C=1, iters=100, steps=2, warmup=1):
@@ -411,10 +481,15 @@ def main():
     T, B = args.frames, args.batch
     cfg_name = {16: "BASELINE configs[1]", 32: "BASELINE configs[4] geometry"}.get(T, "")
 
-    def i3d_block(math, frames, batch, steps, warmup, what, tuning=None, dist_=None, rank_=0, world_=1):
+    def i3d_block(math, frames, batch, steps, warmup, what, tuning=None, fixed_tuning=None, dist_=None, rank_=0,
+                  world_=1, dump=None):
         """One timed block of the full I3D search -> the bench line's fields for it."""
-        el, roof, m = timed_i3d(torch, dist_, dev, rank_, world_, math, batch, frames, args.iters, steps, warmup, lam1,
-                                lam2, tuning_file=tuning)
+        el, roof, m, (res, rec) = timed_i3d(torch, dist_, dev, rank_, world_, math, batch, frames, args.iters, steps,
+                                            warmup, lam1, lam2, tuning_file=tuning, fixed_tuning=fixed_tuning,
+                                            profile=args.full)
+        if dump and rank_ == 0:
+            dump_outputs(torch, dump, res, rec, frames)
+        del res, rec
         return {
             "metric": f"clips/sec full mask-search (I3D, {frames}f, {args.iters} iters)",
             "value": round(world_ * batch * steps / el, 4), "unit": "clips/s", "steps": steps, "warmup": warmup,
@@ -426,7 +501,8 @@ def main():
     blk = i3d_block(args.math, T, B, args.steps, args.warmup,
                     f"I3D perturbation mask search, {args.iters} iters, synthetic clips [{B},3,{T},224,224] per GPU per step "
                     f"({cfg_name}); init_mask + search + reverse score + Grad-CAM",
-                    tuning=args.tuning, dist_=dist, rank_=rank, world_=world)
+                    tuning=args.tuning, fixed_tuning=TUNING_FILE, dist_=dist, rank_=rank, world_=world,
+                    dump=args.dump_outputs)
     if rank == 0:
         out = {
             "metric": "clips/sec full mask-search (I3D, 16f, 300 iters)" if T == 16 else blk["metric"],
@@ -435,36 +511,36 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": blk["dtype"], "data": "synthetic",
             "config": dict(blk["config"], lam1=lam1, lam2=lam2, sharding=f"clip_id % {world}, one all_gather of records"),
-            "roofline": blk["roofline"],
         }
-        summary = {"headline": {"math": args.math, "clips_per_s": blk["value"],
-                                "roofline_frac": (blk["roofline"] or {}).get("frac"),
-                                "matrix_pipe_frac": ((blk["roofline"] or {}).get("matrix_pipe") or {}).get("frac")}}
-        if world == 1 and not args.no_secondary:
-            sec = {}
-            if T == 16:
-                # BASELINE configs[4]: 32-frame 224^2 clips, head window [4,7,7] (stride_mod_layers="none"):
-                # in the headline arithmetic, and in the configuration's stated form (bf16 activation storage)
-                for key, m, sb, ss in (("s32", args.math, min(16, B), 1), ("s32_bf16act", "bf16act", min(16, B), 2)):
-                    sec[key] = i3d_block(m, 32, sb, ss, 1,
-                                         f"I3D mask search + Grad-CAM on 32-frame clips [{sb},3,32,224,224] per step, "
-                                         f"stride_mod_layers='none' (BASELINE configs[4]"
-                                         f"{'; bf16 activation / gradient storage, fp32 accumulate' if m == 'bf16act' else ''})")
-            for key, m, sb, ss in (("bf16x3", "bf16x3", B, 2), ("fp32_mfma", "fp32", min(16, B), 3)):
-                if m != args.math:
-                    sec[key] = i3d_block(m, T, sb, ss, 1, f"same search, [{sb},3,{T},224,224] per step, {MODES[m][3]}")
-            sec["convlstm"] = convlstm_block(torch, dev)
-            out["secondary"] = sec
-            for key, b_ in sec.items():
-                r = b_.get("roofline") or {}
-                summary[key] = {"clips_per_s": b_["value"], "roofline_frac": r.get("frac"), "bound": r.get("bound"),
-                                "math": b_["config"].get("math", "f32")}
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(args.iters, args.cpu_sample_iters, lam1, lam2, host_cores())
-            summary["cpu_baseline"] = {"clips_per_s": round(out["cpu_baseline"]["value"], 5),
-                                       "cores": out["cpu_baseline"]["cores"], "kind": out["cpu_baseline"]["kind"]}
-        out["summary"] = summary      # LAST key: the figures of every block inside the tail of the line
-        sys.stdout.flush()
+        if args.full:
+            out["roofline"] = blk["roofline"]
+            summary = {"headline": {"math": args.math, "clips_per_s": blk["value"],
+                                    "roofline_frac": (blk["roofline"] or {}).get("frac"),
+                                    "matrix_pipe_frac": ((blk["roofline"] or {}).get("matrix_pipe") or {}).get("frac")}}
+            if world == 1 and not args.no_secondary:
+                sec = {}
+                if T == 16:
+                    # BASELINE configs[4]: 32-frame 224^2 clips, head window [4,7,7] (stride_mod_layers="none"):
+                    # in the headline arithmetic, and in the configuration's stated form (bf16 activation storage)
+                    for key, m, sb, ss in (("s32", args.math, min(16, B), 1), ("s32_bf16act", "bf16act", min(16, B), 2)):
+                        sec[key] = i3d_block(m, 32, sb, ss, 1,
+                                             f"I3D mask search + Grad-CAM on 32-frame clips [{sb},3,32,224,224] per step, "
+                                             f"stride_mod_layers='none' (BASELINE configs[4]"
+                                             f"{'; bf16 activation / gradient storage, fp32 accumulate' if m == 'bf16act' else ''})")
+                for key, m, sb, ss in (("bf16x3", "bf16x3", B, 2), ("fp32_mfma", "fp32", min(16, B), 3)):
+                    if m != args.math:
+                        sec[key] = i3d_block(m, T, sb, ss, 1, f"same search, [{sb},3,{T},224,224] per step, {MODES[m][3]}")
+                sec["convlstm"] = convlstm_block(torch, dev)
+                out["secondary"] = sec
+                for key, b_ in sec.items():
+                    r = b_.get("roofline") or {}
+                    summary[key] = {"clips_per_s": b_["value"], "roofline_frac": r.get("frac"), "bound": r.get("bound"),
+                                    "math": b_["config"].get("math", "f32")}
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(args.iters, args.cpu_sample_iters, lam1, lam2, host_cores())
+                summary["cpu_baseline"] = {"clips_per_s": round(out["cpu_baseline"]["value"], 5),
+                                           "cores": out["cpu_baseline"]["cores"], "kind": out["cpu_baseline"]["kind"]}
+            out["summary"] = summary      # LAST key: the figures of every block inside the tail of the line
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -13,7 +14,8 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_json_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "2", "--iters", "2", "--steps", "1",
-                          "--warmup", "0", "--cpu-sample-iters", "1"], capture_output=True, text=True, timeout=600)
+                          "--warmup", "0", "--cpu-sample-iters", "1", "--full"], capture_output=True, text=True,
+                         timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -31,3 +33,35 @@ def test_bench_json_contract():
     c = d["cpu_baseline"]
     assert c["value"] > 0 and c["cores"] >= 1 and c["kind"] in ("port", "reference") and c["sample"]
     assert d["value"] > 0 and d["ms_per_step"] > 0
+
+
+def test_plain_bench_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full: the headline block only; --steps timed steps; --dump-outputs writes the last step's arrays,
+    the same bits in two runs of the same arguments (no kernel choice by timing)."""
+    dumps = []
+    for run in ("a", "b"):
+        d_out = tmp_path / run
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "2", "--iters", "2", "--steps",
+                              "2", "--warmup", "0", "--dump-outputs", str(d_out)], capture_output=True, text=True,
+                             timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+            assert k in d, k
+        for k in ("roofline", "secondary", "cpu_baseline", "summary"):
+            assert k not in d, k
+        assert d["steps"] == 2 and d["warmup"] == 0 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-2      # 2 clips per step
+        got = {f[:-4]: np.load(d_out / f) for f in os.listdir(d_out)}
+        assert sum((d_out / f).stat().st_size for f in os.listdir(d_out)) <= 64_000_000
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert got["clip_id"].tolist() == [2.0, 3.0]                                 # the second (last) step's clips
+        assert got["time_mask"].shape == (2, 16) and got["gradcam"].shape == (2, 16, 224, 224)
+        assert np.all((got["time_mask"] > 0) & (got["time_mask"] < 1))
+        assert sorted(got["ranking"][0].tolist()) == list(range(16))
+        dumps.append(got)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """HBM bytes per launch from two rocprofv3 --pmc passes (dev tool).
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d A -- python3 bench.py ...
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d B -- python3 bench.py ...
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d A -- python3 bench.py --full ...
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d B -- python3 bench.py --full ...
     python tools/pmc_traffic.py A B <batch> out.json
 
     python tools/pmc_traffic.py A B <batch> out.json [bench_line.json] [math] [frames]

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd "$R"
 O=gpurun_out/prof; mkdir -p $O
-B="--math $MATH --batch $BATCH --no-secondary --no-cpu-baseline --tuning $O/${TAG}_bench_tuning.json"
+B="--math $MATH --batch $BATCH --full --no-secondary --no-cpu-baseline --tuning $O/${TAG}_bench_tuning.json"
 rm -f $O/${TAG}_bench_tuning.json
 python bench.py --steps 1 --warmup 0 --iters 4 $B > /dev/null 2>&1
 rocprofv3 --kernel-trace --stats -d "$R/$O/stats" -o s --output-format csv -- python3 bench.py --steps 2 --warmup 1 $B > $O/${TAG}_bench_under_rocprof.json 2> $O/stats.err
