@@ -117,6 +117,28 @@ int ivf_rank_frames(const float* mask, int B, int T, int* order, ivf_stream_t st
 int ivf_init_central_select(const float* orig, const float* full, const float* central, int B, int n, int T,
                             float threshold, float* raw_mask, int* chosen_i, float* ratio, ivf_stream_t stream);
 
+/* Exhaustive one-blob temporal mask search, maskType 'combi' (find_masks docstring, smth:137-141: "iterate through
+ * the different combinations of a coherent 'one blob' mask.  Does not use grad desc").  Candidates are the binary
+ * masks m_{a,L} = 1 on [a, a+L), 1 <= L <= max_len, 0 <= a <= T-L, in canonical order L ascending then a ascending:
+ * k(a,L) = sum_{l<L} (T-l+1) + a.  At a binary mask both perturbations are frame gathers: freeze puts frame
+ * max(a-1,0) on the blob (mask.py:11-22), reverse puts frame 2a+L-1-u on frame u (mask.py:24-56).
+ * ivf_blob_count: host, n = sum_{L=1}^{max_len} (T-L+1), or -1 (message set) unless 1 <= max_len <= T <= 64. */
+int ivf_blob_count(int T, int max_len);
+/* Write candidates [first, first+count) of the flattened (clip, candidate) list of b clips x [b,C,T,HW] (row j =
+ * clip (first+j)/n, candidate (first+j)%n) into p: out_cpad 4 = the I3D plan's input layout [count,T,HW,4]
+ * (16-byte pixels, C <= 4), out_cpad 0 = NCTHW [count,C,T,HW].  mode 0 freeze, 1 reverse. */
+int ivf_blob_stage(const float* x, int b, int C, int T, int HW, int max_len, int mode, long long first, int count,
+                   float* p, int out_cpad, ivf_stream_t stream);
+/* Selection over a score grid scores [b,n] (n = ivf_blob_count(T, max_len)), one clip per thread:
+ * J_k = lam1*sum(m_k) + lam2*TV33(m_k) + s_k with the search loop's fp32 regulariser (ivf_mask_reg), obj [b,n]
+ * (optional); best [b,2] = (a,L) of argmin J, ties to the smaller L then the smaller a, NaN skipped, best_obj [b]
+ * (optional); minimal [b,2] (optional) = init_mask('central')'s criterion (mask.py:121-154) over one-blob masks:
+ * r = (orig - s) / (orig - full), the smallest L with some r >= threshold, the largest r within it, then the smaller
+ * a; (-1,-1) if none qualifies. */
+int ivf_blob_select(const float* scores, const float* orig, const float* full, int b, int T, int max_len, float lam1,
+                    float lam2, float threshold, int* best, float* best_obj, float* obj, int* minimal,
+                    ivf_stream_t stream);
+
 /* Clip ingest: the arithmetic of ImLoader.__getitem__ /
  * KTHImLoader.__getitem__ after the JPEG decode (data_loader_jpg.py:29-37,
  * data_loader_kth.py:25-44): uint8 frames [B][T][H][W][C] -> float32 (exact), permuted to
@@ -385,6 +407,12 @@ int ivf_i3d_search(ivf_i3d_t* net, const float* x, int b, const int* target, flo
 int ivf_i3d_perturbed_forward(ivf_i3d_t* net, const float* x, int b, const float* mask, int mode,
                               float* probs, ivf_stream_t stream);
 
+/* Scores of every one-blob candidate of b clips (see ivf_blob_count): scores [b,n] = probs[target[clip]] of the
+ * perturbed clip under mode (0 freeze, 1 reverse).  Runs the grid in chunks of the plan's B rows (stage -> forward ->
+ * pick), chunks crossing clip boundaries; one stream, no host sync, no allocation. */
+int ivf_i3d_blob_scores(ivf_i3d_t* net, const float* x, int b, const int* target, int max_len, int mode,
+                        float* scores, ivf_stream_t stream);
+
 /* GradCamVideo.__call__ for archType "I3D" / target layer Mixed_5c,
  * grad_cam_videos.py:64-142, for b clips.  target[b] (device) selects the class;
  * cam [b,T'*(T/T'),out_h,out_w] (input_spatial_size, grad_cam_videos.py:54-57);
@@ -452,6 +480,9 @@ int ivf_clstm_search(ivf_clstm_t* net, const float* x, int b, const int* target,
                      ivf_stream_t stream);
 int ivf_clstm_perturbed_forward(ivf_clstm_t* net, const float* x, int b, const float* mask, int mode,
                                 float* probs, ivf_stream_t stream);
+/* ivf_i3d_blob_scores with the ConvLSTM backbone (candidates staged NCTHW). */
+int ivf_clstm_blob_scores(ivf_clstm_t* net, const float* x, int b, const int* target, int max_len, int mode,
+                          float* scores, ivf_stream_t stream);
 
 /* Per-layer kernel selection.  ivf_i3d_autotune times every candidate variant of every
  * convolution (forward and backward-data) on `b` clips and keeps the fastest; the result is

@@ -19,10 +19,12 @@ _state = {"sub_dir": "run0"}
 
 def find_masks(dat_loader, model, config, lam1, lam2, N, ita=1, maskType="gradient", temporalMaskType="freeze",
                classOI=None, verbose=True, maxMaskLength=None, doGradCam=False, runTempMask=True):
-    """KTH:126-380."""
+    """KTH:126-380.  maskType 'combi': the exhaustive one-blob search (KTH:138-142), masks of length <=
+    maxMaskLength; any other maskType keeps the gradient search."""
     return ivf_find_masks.find_masks_impl(
         dat_loader, model, config, lam1, lam2, N, temporalMaskType, classOI, verbose, doGradCam, runTempMask,
-        flavour="kth", sub_dir=_state["sub_dir"], gradcam_size=(RESIZE_SIZE_HEIGHT, RESIZE_SIZE_WIDTH))
+        flavour="kth", sub_dir=_state["sub_dir"], gradcam_size=(RESIZE_SIZE_HEIGHT, RESIZE_SIZE_WIDTH),
+        mask_mode="combi" if maskType == "combi" else "central", max_mask_length=maxMaskLength)
 
 
 def build_model(config, args, device):

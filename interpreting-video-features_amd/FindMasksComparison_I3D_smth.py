@@ -23,12 +23,14 @@ _state = {"sub_dir": "run0"}
 
 def find_masks(dat_loader, model, hyper_params, lam1, lam2, N, maskType="gradient", temporalMaskType="freeze",
                classOI=None, verbose=True, maxMaskLength=None, doGradCam=False, runTempMask=True):
-    """smth:125-315.  maskType is accepted for compatibility: the reference hard-codes
-    mode="central" (smth:190)."""
+    """smth:125-315.  maskType 'combi' runs the exhaustive one-blob search over masks of length <= maxMaskLength
+    (smth:137-141, no gradient descent; N is unused); any other maskType keeps the gradient search from
+    init_mask(mode="central"), which the reference hard-codes (smth:190)."""
     return ivf_find_masks.find_masks_impl(
         dat_loader, model, hyper_params, lam1, lam2, N, temporalMaskType, classOI, verbose, doGradCam,
         runTempMask, flavour="smth", sub_dir=_state["sub_dir"],
-        gradcam_size=(RESIZE_SIZE_HEIGHT, RESIZE_SIZE_WIDTH))
+        gradcam_size=(RESIZE_SIZE_HEIGHT, RESIZE_SIZE_WIDTH),
+        mask_mode="combi" if maskType == "combi" else "central", max_mask_length=maxMaskLength)
 
 
 def main(argv=None):

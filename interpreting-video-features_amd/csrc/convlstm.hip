@@ -1380,3 +1380,25 @@ extern "C" int ivf_clstm_perturbed_forward(ivf_clstm_t* n, const float* x, int b
   }
   return clstm_run_forward(n, P, b, nullptr, probs, s);
 }
+
+// Exhaustive one-blob search (maskType 'combi'), as ivf_i3d_blob_scores: candidates staged into the NCTHW buffer P.
+extern "C" int ivf_clstm_blob_scores(ivf_clstm_t* n, const float* x, int b, const int* target, int max_len, int mode,
+                                     float* scores, ivf_stream_t stream) {
+  IVF_PROPAGATE(clstm_ready(n, 1));
+  IVF_CHECK_ARG(x && target && scores, "clstm_blob_scores: null pointer");
+  IVF_CHECK_ARG(b > 0, "clstm_blob_scores: bad batch %d", b);
+  IVF_CHECK_ARG(mode == 0 || mode == 1, "clstm_blob_scores: mode must be 0 (freeze) or 1 (reverse)");
+  const ivf_clstm_config& c = n->cfg;
+  const int nc = ivf_blob_count(c.T, max_len);
+  if (nc < 0) return IVF_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  float* P = n->at<float>(n->off_p);
+  const long long total = (long long)b * nc;
+  for (long long first = 0; first < total; first += c.B) {
+    const int cnt = (int)std::min<long long>(c.B, total - first);
+    IVF_PROPAGATE(ivf_blob_stage(x, b, c.C, c.T, c.H * c.W, max_len, mode, first, cnt, P, 0, s));
+    IVF_PROPAGATE(clstm_run_forward(n, P, cnt, nullptr, nullptr, s));
+    IVF_PROPAGATE(blob_pick(n->at<float>(n->off_probs), target, c.num_classes, nc, first, cnt, scores, s));
+  }
+  return IVF_OK;
+}

@@ -880,6 +880,29 @@ extern "C" int ivf_i3d_perturbed_forward(ivf_i3d_t* net, const float* x, int b, 
   return run_forward(net, b, nullptr, probs, s);
 }
 
+// Exhaustive one-blob search (maskType 'combi'): the b*n candidates of b clips run in chunks of the plan's B rows --
+// stage straight into the input buffer, forward, pick the target score -- all on one stream, no host sync, no
+// allocation.  Chunks cross clip boundaries, so one clip still fills the plan.
+extern "C" int ivf_i3d_blob_scores(ivf_i3d_t* net, const float* x, int b, const int* target, int max_len, int mode,
+                                   float* scores, ivf_stream_t stream) {
+  IVF_PROPAGATE(check_ready(net, 1));
+  IVF_CHECK_ARG(x && target && scores, "i3d_blob_scores: null pointer");
+  IVF_CHECK_ARG(b > 0, "i3d_blob_scores: bad batch %d", b);
+  IVF_CHECK_ARG(mode == 0 || mode == 1, "i3d_blob_scores: mode must be 0 (freeze) or 1 (reverse)");
+  const ivf_i3d_config& c = net->cfg;
+  const int n = ivf_blob_count(c.T, max_len);
+  if (n < 0) return IVF_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const long long total = (long long)b * n;
+  for (long long first = 0; first < total; first += c.B) {
+    const int cnt = (int)std::min<long long>(c.B, total - first);
+    IVF_PROPAGATE(ivf_blob_stage(x, b, c.C, c.T, c.H * c.W, max_len, mode, first, cnt, net->act(0), 4, s));
+    IVF_PROPAGATE(run_forward(net, cnt, nullptr, nullptr, s));
+    IVF_PROPAGATE(blob_pick(net->at<float>(net->off_probs), target, c.num_classes, n, first, cnt, scores, s));
+  }
+  return IVF_OK;
+}
+
 extern "C" int ivf_i3d_gradcam(ivf_i3d_t* net, const float* x, int b, const int* target, int per_frame,
                                int out_h, int out_w, float* cam, float* probs, ivf_stream_t stream) {
   IVF_PROPAGATE(check_ready(net, b));

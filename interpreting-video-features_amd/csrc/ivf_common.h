@@ -19,6 +19,10 @@ bool prof_begin(hipStream_t s, int variant);
 void prof_end(hipStream_t s);
 void prof_name(int variant, const char* fmt, ...);   // kernel name of a profiler class (first call wins)
 
+// one-blob search (mask_ops.hip): scores[first + j] = probs[j][target[(first + j) / n]] for the `count` rows of a chunk
+int blob_pick(const float* probs, const int* target, int K, int n, long long first, int count, float* scores,
+              hipStream_t s);
+
 #define IVF_CHECK_ARG(cond, ...)                 \
   do {                                           \
     if (!(cond)) {                               \

@@ -4,6 +4,8 @@
 //
 // Reference: video_features_pytorch/mask.py:4-100 and the loop body of
 // FindMasksComparison_I3D_smth.py:198-214.
+#include <type_traits>
+
 #include "ivf_common.h"
 
 namespace ivf {
@@ -797,6 +799,186 @@ extern "C" int ivf_init_central_select(const float* orig, const float* full, con
 extern "C" int ivf_sigmoid(const float* x, float* y, int n, ivf_stream_t stream) {
   IVF_CHECK_ARG(x && y && n > 0, "sigmoid: bad args");
   hipLaunchKernelGGL(sigmoid_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, x, y, n);
+  IVF_CHECK_LAUNCH();
+  return IVF_OK;
+}
+
+// ---------------------------------------------------------------- one-blob exhaustive search (maskType 'combi')
+// The reference's third mask mode (find_masks docstring, FindMasksComparison_I3D_smth.py:137-141): every coherent
+// one-blob binary mask m_{a,L} = 1 on [a, a+L), 1 <= L <= max_len, in the canonical order L ascending then a
+// ascending, k(a,L) = sum_{l<L} (T-l+1) + a.  At a binary mask both perturbations are exact frame gathers (finite
+// inputs): freeze puts frame max(a-1,0) on every frame of the blob (mask.py:11-22; frame 0 is never perturbed),
+// reverse puts frame 2a+L-1-u on frame u (mask.py:24-56, one run).  So the candidates are written straight from the
+// clip into the network's staged-input buffer; the K copies never exist in NCTHW.
+namespace ivf {
+
+__device__ __forceinline__ void blob_decode(int k, int T, int* a, int* L) {
+  int l = 1;
+  while (k >= T - l + 1) {
+    k -= T - l + 1;
+    ++l;
+  }
+  *a = k;
+  *L = l;
+}
+
+__device__ __forceinline__ int blob_src(int u, int a, int L, int mode) {
+  if (u < a || u >= a + L) return u;
+  return mode == 0 ? (a > 0 ? a - 1 : 0) : 2 * a + L - 1 - u;
+}
+
+// channels-last: one thread per (row, pixel), all C <= 4 channels, one 16-byte pixel per frame (the layout
+// freeze_fwd_cl4_kernel writes); row j = candidate `first + j` of the flattened (clip, candidate) list
+__global__ void blob_stage_cl4_kernel(const float* __restrict__ x, float* __restrict__ p, int C, int T, int HW,
+                                      int n, long long first, int count, int mode) {
+  size_t total = (size_t)count * HW;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total;
+       i += (size_t)gridDim.x * blockDim.x) {
+    int px = i % HW;
+    int j = i / HW;
+    long long g = first + j;
+    int clip = (int)(g / n), a, L;
+    blob_decode((int)(g % n), T, &a, &L);
+    const float* xc = x + (size_t)clip * C * T * HW + px;
+    for (int u = 0; u < T; ++u) {
+      int su = blob_src(u, a, L, mode);
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+      for (int c = 0; c < C; ++c) v[c] = xc[((size_t)c * T + su) * HW];
+      *reinterpret_cast<float4*>(p + ((size_t)j * T + u) * HW * 4 + (size_t)px * 4) =
+          make_float4(v[0], v[1], v[2], v[3]);
+    }
+  }
+}
+
+// NCTHW: one thread per (row, channel, 4-pixel quad) when HW % 4 == 0 (16-byte loads and stores), else per pixel
+template <int V>
+__global__ void blob_stage_ncthw_kernel(const float* __restrict__ x, float* __restrict__ p, int C, int T, int HW,
+                                        int n, long long first, int count, int mode) {
+  using vec = typename std::conditional<V == 4, float4, float>::type;
+  const int HWv = HW / V;
+  size_t total = (size_t)count * C * HWv;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total;
+       i += (size_t)gridDim.x * blockDim.x) {
+    int q = i % HWv;
+    int c = (i / HWv) % C;
+    int j = i / ((size_t)HWv * C);
+    long long g = first + j;
+    int clip = (int)(g / n), a, L;
+    blob_decode((int)(g % n), T, &a, &L);
+    const vec* xc = reinterpret_cast<const vec*>(x + ((size_t)clip * C + c) * T * HW) + q;
+    vec* pc = reinterpret_cast<vec*>(p + ((size_t)j * C + c) * T * HW) + q;
+    for (int u = 0; u < T; ++u) pc[(size_t)u * HWv] = xc[(size_t)blob_src(u, a, L, mode) * HWv];
+  }
+}
+
+// scores[clip][k] = probs[j][target[clip]] for the rows of one chunk (NaN for a target outside [0,K))
+__global__ void blob_pick_kernel(const float* __restrict__ probs, const int* __restrict__ target, int K, int n,
+                                 long long first, int count, float* __restrict__ scores) {
+  int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= count) return;
+  long long g = first + j;
+  int clip = (int)(g / n);
+  int t = target[clip];
+  scores[g] = (t >= 0 && t < K) ? probs[(size_t)j * K + t] : __builtin_nanf("");
+}
+
+// Selection, one thread per clip.  J_k = lam1*sum(m_k) + lam2*TV33(m_k) + s_k with the search loop's own fp32
+// regulariser arithmetic (mask_reg_kernel / tv_norm_dev, summed in the order of the loop's traj row); best = argmin J
+// (first in canonical order on a tie, NaN skipped); minimal = smallest L with some r = (orig-s)/(orig-full) >=
+// threshold, the largest r within it, then the smallest a (mask.py:121-154's criterion over one-blob masks).
+__global__ void blob_select_kernel(const float* __restrict__ scores, const float* __restrict__ orig,
+                                   const float* __restrict__ full, int B, int T, int max_len, int n, float lam1,
+                                   float lam2, float threshold, int* __restrict__ best, float* __restrict__ best_obj,
+                                   float* __restrict__ obj, int* __restrict__ minimal) {
+  int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float* s = scores + (size_t)b * n;
+  const float den = orig[b] - full[b];
+  float m[MAX_T];
+  int bk = -1, ba = -1, bl = -1, ma = -1, ml = -1;
+  float bj = 0.f, mr = 0.f;
+  int k = 0;
+  for (int L = 1; L <= max_len; ++L) {
+    for (int a = 0; a + L <= T; ++a, ++k) {
+      float l1 = 0.f;
+      for (int u = 0; u < T; ++u) {
+        m[u] = (u >= a && u < a + L) ? 1.f : 0.f;
+        l1 += fabsf(m[u]);
+      }
+      float tv;
+      tv_norm_dev(m, T, 3.f, 3.f, &tv, nullptr, 1.f);
+      const float J = lam1 * l1 + lam2 * tv + s[k];
+      if (obj) obj[(size_t)b * n + k] = J;
+      if (J == J && (bk < 0 || J < bj)) { bk = k; bj = J; ba = a; bl = L; }
+      if (ml < 0 || ml == L) {
+        const float r = (orig[b] - s[k]) / den;
+        if (r >= threshold && (ml < 0 || r > mr)) { ma = a; ml = L; mr = r; }
+      }
+    }
+  }
+  best[b * 2 + 0] = ba;
+  best[b * 2 + 1] = bl;
+  if (best_obj) best_obj[b] = bk < 0 ? __builtin_nanf("") : bj;
+  if (minimal) {
+    minimal[b * 2 + 0] = ma;
+    minimal[b * 2 + 1] = ml;
+  }
+}
+
+int blob_pick(const float* probs, const int* target, int K, int n, long long first, int count, float* scores,
+              hipStream_t s) {
+  hipLaunchKernelGGL(blob_pick_kernel, dim3(cdiv(count, 64)), dim3(64), 0, s, probs, target, K, n, first, count,
+                     scores);
+  IVF_CHECK_LAUNCH();
+  return IVF_OK;
+}
+
+}  // namespace ivf
+
+extern "C" int ivf_blob_count(int T, int max_len) {
+  if (T < 1 || T > MAX_T || max_len < 1 || max_len > T) {
+    set_error("blob_count: need 1 <= max_len (%d) <= T (%d) <= %d", max_len, T, MAX_T);
+    return -1;
+  }
+  return max_len * (T + 1) - max_len * (max_len + 1) / 2;
+}
+
+extern "C" int ivf_blob_stage(const float* x, int b, int C, int T, int HW, int max_len, int mode, long long first,
+                              int count, float* p, int out_cpad, ivf_stream_t stream) {
+  IVF_CHECK_ARG(x && p, "blob_stage: null pointer");
+  IVF_CHECK_ARG(b > 0 && C > 0 && HW > 0, "blob_stage: bad dims");
+  const int n = ivf_blob_count(T, max_len);
+  if (n < 0) return IVF_ERR_BAD_ARG;
+  IVF_CHECK_ARG(mode == 0 || mode == 1, "blob_stage: mode must be 0 (freeze) or 1 (reverse)");
+  IVF_CHECK_ARG(first >= 0 && count > 0 && first + count <= (long long)b * n,
+                "blob_stage: rows [%lld, %lld) outside the %lld candidates of %d clips", first, first + count,
+                (long long)b * n, b);
+  IVF_CHECK_ARG(out_cpad == 0 || (out_cpad == 4 && C <= 4),
+                "blob_stage: out_cpad must be 0 (NCTHW) or 4 (16-byte channels-last, C <= 4)");
+  hipStream_t s = (hipStream_t)stream;
+  if (out_cpad == 4) {
+    hipLaunchKernelGGL(blob_stage_cl4_kernel, dim3(grid_for((size_t)count * HW)), dim3(256), 0, s, x, p, C, T, HW,
+                       n, first, count, mode);
+  } else if (HW % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)p & 15) == 0) {
+    hipLaunchKernelGGL(blob_stage_ncthw_kernel<4>, dim3(grid_for((size_t)count * C * HW / 4)), dim3(256), 0, s, x, p,
+                       C, T, HW, n, first, count, mode);
+  } else {
+    hipLaunchKernelGGL(blob_stage_ncthw_kernel<1>, dim3(grid_for((size_t)count * C * HW)), dim3(256), 0, s, x, p, C,
+                       T, HW, n, first, count, mode);
+  }
+  IVF_CHECK_LAUNCH();
+  return IVF_OK;
+}
+
+extern "C" int ivf_blob_select(const float* scores, const float* orig, const float* full, int b, int T, int max_len,
+                               float lam1, float lam2, float threshold, int* best, float* best_obj, float* obj,
+                               int* minimal, ivf_stream_t stream) {
+  IVF_CHECK_ARG(scores && orig && full && best, "blob_select: null pointer");
+  IVF_CHECK_ARG(b > 0, "blob_select: bad batch %d", b);
+  const int n = ivf_blob_count(T, max_len);
+  if (n < 0) return IVF_ERR_BAD_ARG;
+  hipLaunchKernelGGL(blob_select_kernel, dim3(cdiv(b, 64)), dim3(64), 0, (hipStream_t)stream, scores, orig, full, b,
+                     T, max_len, n, lam1, lam2, threshold, best, best_obj, obj, minimal);
   IVF_CHECK_LAUNCH();
   return IVF_OK;
 }

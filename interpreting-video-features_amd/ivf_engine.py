@@ -31,6 +31,25 @@ def _mode_id(mode):
     raise UnboundLocalError("local variable 'perturbed_input' referenced before assignment")
 
 
+def _blob_scores(eng, fn, x, target, max_len, mode):
+    """Shared body of I3DEngine.blob_scores / CLSTMEngine.blob_scores: the whole one-blob grid of b clips in one C
+    call (chunks of the plan's max_batch rows; b itself may exceed max_batch)."""
+    L.require_gpu(x)
+    x = L.f32c(x)
+    if x.dim() != 5 or tuple(x.shape[1:]) != eng.clip_shape:
+        raise L.IvfError(f"clip batch must be [b,{','.join(map(str, eng.clip_shape))}], got {tuple(x.shape)}")
+    b, T = x.shape[0], eng.clip_shape[1]
+    ml = T if max_len is None else int(max_len)
+    n = L.lib().ivf_blob_count(T, ml)
+    if n < 0:
+        raise L.IvfError(L.lib().ivf_last_error().decode())
+    tgt = eng._targets(target, b)
+    scores = torch.empty(b, n, device=eng.device)
+    with torch.cuda.device(eng.device):
+        L.check(fn(eng._h, L.ptr(x), b, L.ptr(tgt), ml, _mode_id(mode), L.ptr(scores), L.stream()))
+    return scores
+
+
 def _arena(nbytes, device):
     # torch's caching allocator returns >=512-byte aligned blocks
     t = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
@@ -240,6 +259,11 @@ class I3DEngine:
                                                       _mode_id(mode), L.ptr(probs), L.stream()))
         return probs
 
+    def blob_scores(self, x, target, max_len=None, mode="freeze"):
+        """Exhaustive one-blob search grid (maskType 'combi', ivf_i3d_blob_scores): scores [b, n] of target[clip]
+        under every one-blob binary mask, in the order of ivf_search.blob_candidates(T, max_len)."""
+        return _blob_scores(self, L.lib().ivf_i3d_blob_scores, x, target, max_len, mode)
+
     def argmax(self, probs):
         b = probs.shape[0]
         t = torch.empty(b, dtype=torch.int32, device=self.device)
@@ -389,6 +413,10 @@ class CLSTMEngine:
             L.check(L.lib().ivf_clstm_perturbed_forward(self._h, L.ptr(x), b, L.ptr(mask),
                                                         _mode_id(mode), L.ptr(probs), L.stream()))
         return probs
+
+    def blob_scores(self, x, target, max_len=None, mode="freeze"):
+        """I3DEngine.blob_scores with the ConvLSTM backbone (ivf_clstm_blob_scores)."""
+        return _blob_scores(self, L.lib().ivf_clstm_blob_scores, x, target, max_len, mode)
 
     def gradcam(self, *a, **kw):
         raise L.IvfError("Grad-CAM for the PyTorch ConvLSTM cannot run in the reference either "

@@ -45,7 +45,11 @@ def _unwrap(model):
 
 def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMaskType="freeze", classOI=None,
                     verbose=True, doGradCam=False, runTempMask=True, flavour="smth", sub_dir="run0",
-                    results_path="results/", gradcam_size=None, write_files=True, device=None, visualise=True):
+                    results_path="results/", gradcam_size=None, write_files=True, device=None, visualise=True,
+                    mask_mode="central", max_mask_length=None, blob_batch=32):
+    """mask_mode 'combi' (the drivers' maskType='combi', smth:137-141) replaces init_mask + Adam by the exhaustive
+    one-blob search over masks of length <= max_mask_length; its plan holds at least blob_batch clips so that the
+    candidates of a loader batch fill it.  Its records also carry blob_start, blob_length and blob_scores."""
     net = _unwrap(model)
     net.eval()                                                      # smth:145
     flt = _class_filter(classOI)
@@ -67,11 +71,12 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
         if not keep:
             continue
         xs = x[keep].contiguous()
-        eng = net._engine_for(xs)
+        eng = net._engine_for(xs, min_batch=blob_batch) if mask_mode == "combi" else net._engine_for(xs)
         search = ivf_search.MaskSearch(eng, lam1, lam2, N, temporalMaskType, threshold=0.9, lr=0.2,
                                        grad_cam_type=hyper_params.get("gradCamType", "guessed"),
                                        do_gradcam=doGradCam, run_temp_mask=runTempMask,
-                                       normalize_per_frame=True, gradcam_size=gradcam_size)
+                                       normalize_per_frame=True, gradcam_size=gradcam_size, mask_mode=mask_mode,
+                                       max_mask_length=max_mask_length)
         res = search.run(xs, labels[keep])
         host = {k: v.detach().cpu() for k, v in res.items() if k != "gradcam"}
         if doGradCam:
@@ -98,6 +103,9 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                      'time_mask': tm,
                                      'original_score_guess': int(gs) if flavour == "smth" else gs,
                                      'original_score_true': cs, 'freeze_score': fz, 'reverse_score': rv})
+                if mask_mode == "combi":
+                    time_results[-1].update(blob_start=int(host["blob"][j, 0]), blob_length=int(host["blob"][j, 1]),
+                                            blob_scores=host["blob_scores"][j].numpy())
                 tmask = res["time_mask"][j].clone()     # the clip's own [T] tensor, as the reference's time_mask
                 if verbose:
                     print("resulting mask is: ", tmask)

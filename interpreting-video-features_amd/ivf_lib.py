@@ -81,6 +81,9 @@ _SIGS = {
     "ivf_sigmoid": (c_int, [_P, _P, _I, _P]),
     "ivf_rank_frames": (c_int, [_P, _I, _I, _P, _P]),
     "ivf_init_central_select": (c_int, [_P, _P, _P, _I, _I, _I, c_float, _P, _P, _P, _P]),
+    "ivf_blob_count": (c_int, [_I, _I]),
+    "ivf_blob_stage": (c_int, [_P, _I, _I, _I, _I, _I, _I, ctypes.c_longlong, _I, _P, _I, _P]),
+    "ivf_blob_select": (c_int, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
     "ivf_clip_ingest_u8": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ivf_conv3d": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
     "ivf_bn_fold": (c_int, [_P, _P, _P, _P, _F, _P, _P, _I, _P]),
@@ -119,6 +122,7 @@ _SIGS = {
     "ivf_i3d_act_elem_bytes": (c_int, [_P]),
     "ivf_i3d_search": (c_int, [_P, _P, _I, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _I, _I, _I, _P, _P]),
     "ivf_i3d_perturbed_forward": (c_int, [_P, _P, _I, _P, _I, _P, _P]),
+    "ivf_i3d_blob_scores": (c_int, [_P, _P, _I, _P, _I, _I, _P, _P]),
     "ivf_i3d_gradcam": (c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "ivf_i3d_gradcam_layer": (c_int, [_P, _P, _I, _P, c_char_p, _I, _I, _I, _P, _P, _P]),
     "ivf_i3d_conv_flops_per_clip": (ctypes.c_double, [_P]),
@@ -153,6 +157,7 @@ _SIGS_OPT = {
     "ivf_clstm_backward": (c_int, [_P, _I, _P, _P, _P, _P, _P]),
     "ivf_clstm_search": (c_int, [_P, _P, _I, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _I, _I, _I, _P, _P]),
     "ivf_clstm_perturbed_forward": (c_int, [_P, _P, _I, _P, _I, _P, _P]),
+    "ivf_clstm_blob_scores": (c_int, [_P, _P, _I, _P, _I, _I, _P, _P]),
     # csrc/tf_clstm.hip (documented extension)
     "ivf_tfclstm_create": (c_int, [POINTER(TFCLSTMConfig), POINTER(c_void_p)]),
     "ivf_tfclstm_destroy": (None, [_P]),

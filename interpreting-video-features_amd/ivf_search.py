@@ -83,10 +83,62 @@ def frame_ranking(mask):
     return order.long()
 
 
+def blob_candidates(T, max_len=None):
+    """The one-blob candidates of maskType 'combi' (smth:137-141) as a host int64 table [n, 2] of (a, L): every
+    binary mask that is 1 on [a, a+L), 1 <= L <= max_len (default T), in canonical order (L, then a)."""
+    ml = T if max_len is None else int(max_len)
+    n = L.lib().ivf_blob_count(int(T), ml)
+    if n < 0:
+        raise L.IvfError(L.lib().ivf_last_error().decode())
+    rows = [(a, ln) for ln in range(1, ml + 1) for a in range(T - ln + 1)]
+    return torch.tensor(rows, dtype=torch.int64).reshape(n, 2)
+
+
+def blob_select(scores, orig, full, T, max_len=None, lam1=0.01, lam2=0.02, threshold=0.9, want_obj=False):
+    """ivf_blob_select on a score grid [b, n]: dict of device tensors best [b,2] (a, L of argmin J), objective [b]
+    (its J), minimal [b,2] (smallest sufficient blob, (-1,-1) if none) and, with want_obj, obj [b,n]."""
+    s = L.f32c(scores)
+    L.require_gpu(s)
+    b = s.shape[0]
+    ml = T if max_len is None else int(max_len)
+    orig, full = L.f32c(orig.reshape(b)), L.f32c(full.reshape(b))
+    best = torch.empty(b, 2, dtype=torch.int32, device=s.device)
+    minimal = torch.empty(b, 2, dtype=torch.int32, device=s.device)
+    bobj = torch.empty(b, device=s.device)
+    obj = torch.empty_like(s) if want_obj else None
+    with torch.cuda.device(s.device):
+        L.check(L.lib().ivf_blob_select(L.ptr(s), L.ptr(orig), L.ptr(full), b, int(T), ml, float(lam1), float(lam2),
+                                        float(threshold), L.ptr(best), L.ptr(bobj), L.ptr(obj), L.ptr(minimal),
+                                        L.stream()))
+    out = dict(best=best.long(), objective=bobj, minimal=minimal.long())
+    if want_obj:
+        out["obj"] = obj
+    return out
+
+
+def blob_index(blob, T):
+    """Grid column k(a, L) = sum_{l<L} (T-l+1) + a of (a, L) rows [b,2]; -1 where L < 1."""
+    a, ln = blob[:, 0], blob[:, 1]
+    k = (ln - 1) * (T + 1) - (ln - 1) * ln // 2 + a
+    return torch.where(ln >= 1, k, torch.full_like(k, -1))
+
+
+def blob_masks(best, T):
+    """Binary float masks [b, T] of (a, L) rows [b, 2]: 1 on [a, a+L) (all zero for L < 1)."""
+    u = torch.arange(T, device=best.device)[None]
+    a, ln = best[:, :1], best[:, 1:]
+    return ((u >= a) & (u < a + ln)).float()
+
+
 class MaskSearch:
     def __init__(self, engine, lam1=0.01, lam2=0.02, n_iter=300, mask_type="freeze", threshold=0.9,
                  lr=0.2, grad_cam_type="guessed", do_gradcam=True, run_temp_mask=True,
-                 normalize_per_frame=True, gradcam_size=None):
+                 normalize_per_frame=True, gradcam_size=None, mask_mode="central", max_mask_length=None):
+        """mask_mode 'central': init_mask('central') + n_iter Adam steps (smth:188-214); 'combi': the exhaustive
+        one-blob search (smth:137-141) over masks of length <= max_mask_length (default T), no gradient descent."""
+        if mask_mode not in ("central", "combi"):
+            raise L.IvfError(f"mask_mode must be 'central' or 'combi', got {mask_mode!r}")
+        self.mask_mode, self.max_mask_length = mask_mode, max_mask_length
         self.engine = engine
         self.lam1, self.lam2, self.n_iter = float(lam1), float(lam2), int(n_iter)
         self.mask_type, self.threshold, self.lr = mask_type, threshold, lr
@@ -111,7 +163,9 @@ class MaskSearch:
         out["target"] = target
         out["original_score_guess"] = probs[idx, pred.long()]
         out["original_score_true"] = probs[idx, labels.long()]
-        if self.run_temp_mask:
+        if self.run_temp_mask and self.mask_mode == "combi":
+            self._run_combi(x, target, probs, out)
+        elif self.run_temp_mask:
             raw, info = init_masks_central(eng, x, target, probs[idx, target.long()], self.threshold,
                                            self.mask_type)                   # smth:188-190
             out["init_mask"] = raw.clone()
@@ -133,6 +187,31 @@ class MaskSearch:
             cam, _ = eng.gradcam(x, gc_target, per_frame=self.normalize_per_frame, out_hw=self.gradcam_size)
             out["gradcam"] = cam                                             # smth:269
         return out
+
+
+    def _run_combi(self, x, target, probs, out):
+        """maskType 'combi': score every one-blob mask, pick argmin of the search loss on the device."""
+        eng = self.engine
+        b, T = x.shape[0], x.shape[2]
+        dev = x.device
+        idx = torch.arange(b, device=dev)
+        tl = target.long()
+        orig = probs[idx, tl]
+        full = eng.perturbed_forward(x, torch.ones(b, T, device=dev), "freeze")[idx, tl]     # mask.py:123-128
+        scores = eng.blob_scores(x, target, self.max_mask_length, self.mask_type)
+        sel = blob_select(scores, orig, full, T, self.max_mask_length, self.lam1, self.lam2, self.threshold)
+        mask = blob_masks(sel["best"], T)
+        k = blob_index(sel["best"], T)
+        out["time_mask"] = mask
+        out["freeze_score"] = torch.where(k >= 0, scores[idx, k.clamp(min=0)],
+                                          torch.full((b,), float("nan"), device=dev))     # the loop-type score
+        out["reverse_score"] = eng.perturbed_forward(x, mask, "reverse")[idx, tl]            # smth:234-235
+        out["ranking"] = frame_ranking(mask)
+        out["snapped"] = mask > 0.5
+        out["blob"] = sel["best"]
+        out["blob_objective"] = sel["objective"]
+        out["blob_minimal"] = sel["minimal"]
+        out["blob_scores"] = scores
 
 
 RECORD_INT_FIELDS = ("clip_id", "pred_class", "target")
