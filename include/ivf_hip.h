@@ -484,6 +484,34 @@ int ivf_clstm_perturbed_forward(ivf_clstm_t* net, const float* x, int b, const f
 int ivf_clstm_blob_scores(ivf_clstm_t* net, const float* x, int b, const int* target, int max_len, int mode,
                           float* scores, ivf_stream_t stream);
 
+/* Grad-CAM on the ConvLSTM's pooled layer outputs, stored [B,T,hid,plane] (plane = Hp*Wp), fp32:
+ * weights[b,c] = mean over (selected steps, plane) of grad (grad_cam_videos.py:98), cam[b,e,:] =
+ * relu(sum_c weights[b,c] * feat[b,step_e,c,:]) (:101-110), cam [B,n_steps,plane].  steps_host: n_steps (<= 64)
+ * HOST ints inside [0,T), NULL = 0 .. n_steps-1; they travel as a kernel argument.  One workgroup per
+ * (channel, clip), no atomics: a clip's result does not depend on B. */
+int ivf_clstm_gradcam_reduce(const float* feat, const float* grad, const int* steps_host, int n_steps,
+                             float* weights, float* cam, int B, int T, int hid, int plane, ivf_stream_t stream);
+/* The effective steps that lie inside the clip (convolution_lstm.py:129-130), increasing HOST ints: the map stack
+ * of Grad-CAM target 'clstm'.  Default: the plan's output steps. */
+int ivf_clstm_set_cam_steps(ivf_clstm_t* net, const int* steps_host, int n_steps);
+/* GradCamVideo.__call__ for archType "CLSTM" (grad_cam_videos.py:64-142 over pytorch-grad-cam/grad-cam.py:33-49)
+ * on b clips: forward, backward truncated above the target, reduction, resize + normalise.
+ * layer -1 is the reference's branch: the top layer's pooled outputs at the effective steps (n maps, each
+ * repeated T / n times; cam [b, n*(T/n), out_h, out_w]) with the gradient endFC sends into them.
+ * layer 0 .. layers-1 is an EXTENSION: that layer's pooled output at every step with the gradient of the class
+ * score through the layers above and their recurrences (cam [b,T,out_h,out_w]).
+ * target [b] device ints, NULL = argmax of the output; probs [b,K] optional. */
+int ivf_clstm_gradcam(ivf_clstm_t* net, const float* x, int b, const int* target, int layer, int per_frame,
+                      int out_h, int out_w, float* cam, float* probs, ivf_stream_t stream);
+/* The same up to the reduction: cam [b,n,Hp,Wp] un-resized, weights [b,hid], and copies of the features and
+ * gradients the reduction read, [b,n,hid,Hp,Wp] (n as above); every output optional. */
+int ivf_clstm_gradcam_raw(ivf_clstm_t* net, const float* x, int b, const int* target, int layer, float* cam,
+                          float* weights, float* feat, float* grad, float* probs, ivf_stream_t stream);
+/* Workspace views of one layer after a forward / backward: pooled outputs X and their gradient dX, both
+ * [b,T,hid,Hp,Wp]; every output optional. */
+int ivf_clstm_layer_buffers(ivf_clstm_t* net, int layer, const float** X, const float** dX, int* hid, int* Hp,
+                            int* Wp);
+
 /* Per-layer kernel selection.  ivf_i3d_autotune times every candidate variant of every
  * convolution (forward and backward-data) on `b` clips and keeps the fastest; the result is
  * 2*ivf_i3d_num_conv_ops() ints that can be read and installed again, e.g. broadcast from

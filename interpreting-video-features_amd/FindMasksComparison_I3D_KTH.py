@@ -60,7 +60,7 @@ def main(argv=None):
                                              drop_last=True, device=device)     # val_loader, KTH:73-78
     config.setdefault("gradCamType", args.gradCamType)
     find_masks(loader, model, config, lam1, lam2, N, 1, "central", config.get("maskPerturbType", "freeze"),
-               classOI=None, doGradCam=config['conv_model'].endswith("CLSTM_4") is False, runTempMask=True)
+               classOI=None, doGradCam=True, runTempMask=True)                       # KTH:123
 
 
 if __name__ == '__main__':

@@ -889,6 +889,61 @@ __global__ void clstm_fill_kernel(float* p, long n, float v) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = v;
 }
 
+// ---------------------------------------------------------------- Grad-CAM on the pooled outputs [B,T,hid,plane]
+// The steps of a map stack travel as a kernel argument (T <= 64): no device table, no copy.
+struct CamSteps {
+  int n;
+  int s[64];
+};
+
+// weights[b,c] = mean over (selected steps, plane) of grad[b,step,c,:]   (grad_cam_videos.py:98)
+// One workgroup per (channel, clip), whatever the batch: every thread walks the same elements in the same order,
+// the 64 lanes of a wave meet by shuffles, the 4 waves through LDS and thread 0 adds them in wave order -- so a
+// clip's weights do not depend on how many clips the call holds.  The partial sums are fp64: the gradients are
+// signed values that largely cancel, and the sum is a few thousand terms per thread at most.
+__global__ __launch_bounds__(256) void clstm_cam_weights_kernel(const float* __restrict__ grad, CamSteps st,
+                                                                float* __restrict__ wts, int T, int hid, int plane) {
+  const int c = blockIdx.x, b = blockIdx.y;
+  double acc = 0.0;
+  for (int e = 0; e < st.n; ++e) {
+    const float* g = grad + (((long)b * T + st.s[e]) * hid + c) * plane;
+    for (int i = threadIdx.x; i < plane; i += 256) acc += (double)g[i];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  __shared__ double part[4];
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    wts[(long)b * hid + c] = (float)((((part[0] + part[1]) + part[2]) + part[3]) / ((double)st.n * plane));
+}
+
+// cam[b,e,i] = max(sum_c w[b,c] * feat[b,step_e,c,i], 0): channels in order, unfused, as the reference's
+// `cam += w * target[i]` (grad_cam_videos.py:101-110).  One thread per map pixel.
+__global__ __launch_bounds__(256) void clstm_cam_map_kernel(const float* __restrict__ feat,
+                                                            const float* __restrict__ wts, CamSteps st,
+                                                            float* __restrict__ cam, int T, int hid, int plane) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int e = blockIdx.y, b = blockIdx.z;
+  if (i >= plane) return;
+  const float* f = feat + ((long)b * T + st.s[e]) * hid * plane + i;
+  const float* w = wts + (long)b * hid;
+  float acc = 0.f;
+  for (int c = 0; c < hid; ++c) acc += w[c] * f[(long)c * plane];
+  cam[((long)b * st.n + e) * plane + i] = fmaxf(acc, 0.f);
+}
+
+// out[b,e,:] = src[b,step_e,:] (rows of `row` floats): the map stack of the selected steps, for ivf_clstm_gradcam_raw
+__global__ void clstm_gather_steps_kernel(const float* __restrict__ src, CamSteps st, float* __restrict__ out, int T,
+                                          long row, long total) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    long r = i % row;
+    int e = (i / row) % st.n;
+    long b = i / (row * st.n);
+    out[i] = src[(b * T + st.s[e]) * row + r];
+  }
+}
+
 static inline int grid_for(long total, int block = 256, int cap = 4096) {
   long g = (total + block - 1) / block;
   return (int)(g > cap ? cap : (g ? g : 1));
@@ -915,7 +970,9 @@ struct ivf_clstm {
   int fc_in;     // endFC inputs: feat * number of output steps
   size_t ws_bytes;
   size_t off_p, off_dp, off_flat, off_dflat, off_logits, off_probs, off_score, off_sig, off_terms, off_dreg,
-      off_dsig, off_fbwd, off_pair;
+      off_dsig, off_fbwd, off_pair, off_cam, off_camw, off_cammm, off_camtgt;
+  int n_cam_steps = 0;      // effective steps reached: the map stack of Grad-CAM target 'clstm'
+  int cam_steps[64];
   float* wa = nullptr;
   char* ws = nullptr;
   std::vector<bool> cell_loaded;
@@ -1015,6 +1072,13 @@ extern "C" int ivf_clstm_create(const ivf_clstm_config* c, ivf_clstm_t** out) {
   n->off_dsig = takeb(B * T * 4);
   n->off_fbwd = takeb(ivf_freeze_bwd_workspace_bytes((int)B, (int)T));
   n->off_pair = takeb(B * T * 8);
+  // Grad-CAM: raw maps of the largest pooled plane (layer 0) at every step, channel weights, min/max of the resize
+  n->off_cam = takeb(B * T * n->L[0].Hp * n->L[0].Wp * 4);
+  n->off_camw = takeb(B * hid * 4);
+  n->off_cammm = takeb(B * T * 2 * 4);
+  n->off_camtgt = takeb(B * 4);
+  n->n_cam_steps = n->cfg.n_out_steps;
+  for (int e = 0; e < n->cfg.n_out_steps; ++e) n->cam_steps[e] = n->cfg.out_steps[e];
   n->ws_bytes = bytes;
   n->cell_loaded.assign(c->layers, false);
   *out = n;
@@ -1206,9 +1270,11 @@ static int clstm_run_forward(ivf_clstm* n, const float* x, int b, float* logits,
   return IVF_OK;
 }
 
-// BPTT to the input clip gradient dx (NCTHW)
+// BPTT to the input clip gradient dx (NCTHW).  `stop`: layers L-1 ... stop are processed and nothing below, so
+// that dX_off of layer stop-1 holds the gradient of its pooled outputs; stop = L is the head backward and the
+// scatter into the top layer's dX_off alone.  dx is written for stop = 0 only.
 static int clstm_run_backward(ivf_clstm* n, int b, const int* target, const float* dout, float* score, float* dx,
-                              hipStream_t s) {
+                              hipStream_t s, int stop = 0) {
   const ivf_clstm_config& c = n->cfg;
   const int hid = c.hidden, k = c.kernel, T = c.T;
   const float* sc = c.batch_norm ? n->wa + n->bn_scale_off : nullptr;
@@ -1225,7 +1291,7 @@ static int clstm_run_backward(ivf_clstm* n, int b, const int* target, const floa
     IVF_CHECK_HIP(hipMemcpy2DAsync(n->wsf(top.dX_off) + (size_t)c.out_steps[e] * n->feat, (size_t)T * n->feat * 4,
                                    dflat + (size_t)e * n->feat, (size_t)n->fc_in * 4, (size_t)n->feat * 4, b,
                                    hipMemcpyDeviceToDevice, s));
-  for (int i = (int)n->L.size() - 1; i >= 0; --i) {
+  for (int i = (int)n->L.size() - 1; i >= stop; --i) {
     const LayerPlan& p = n->L[i];
     hipLaunchKernelGGL(clstm_unpool_bwd_kernel, dim3(grid_for((long)b * T * hid * p.Ho * p.Wo)), dim3(256), 0, s,
                        n->wsf(p.dX_off), n->at<unsigned char>(p.arg_off), sc, n->wsf(p.dHp_off), (long)b * T, hid,
@@ -1400,5 +1466,127 @@ extern "C" int ivf_clstm_blob_scores(ivf_clstm_t* n, const float* x, int b, cons
     IVF_PROPAGATE(clstm_run_forward(n, P, cnt, nullptr, nullptr, s));
     IVF_PROPAGATE(blob_pick(n->at<float>(n->off_probs), target, c.num_classes, nc, first, cnt, scores, s));
   }
+  return IVF_OK;
+}
+
+// ---------------------------------------------------------------- Grad-CAM (grad_cam_videos.py:64-142, archType "CLSTM")
+
+static int cam_steps_from(const int* steps, int n_steps, int T, CamSteps* st) {
+  IVF_CHECK_ARG(n_steps > 0 && n_steps <= 64, "clstm_gradcam_reduce: 1..64 steps");
+  st->n = n_steps;
+  for (int e = 0; e < n_steps; ++e) {
+    st->s[e] = steps ? steps[e] : e;
+    IVF_CHECK_ARG(st->s[e] >= 0 && st->s[e] < T, "clstm_gradcam_reduce: step %d outside [0,%d)", st->s[e], T);
+  }
+  return IVF_OK;
+}
+
+extern "C" int ivf_clstm_gradcam_reduce(const float* feat, const float* grad, const int* steps, int n_steps,
+                                        float* weights, float* cam, int B, int T, int hid, int plane,
+                                        ivf_stream_t stream) {
+  IVF_CHECK_ARG(feat && grad && weights && cam, "clstm_gradcam_reduce: null pointer");
+  IVF_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && hid > 0 && plane > 0, "clstm_gradcam_reduce: bad dims");
+  CamSteps st;
+  IVF_PROPAGATE(cam_steps_from(steps, n_steps, T, &st));
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(clstm_cam_weights_kernel, dim3(hid, B), dim3(256), 0, s, grad, st, weights, T, hid, plane);
+  IVF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(clstm_cam_map_kernel, dim3((plane + 255) / 256, n_steps, B), dim3(256), 0, s, feat, weights, st,
+                     cam, T, hid, plane);
+  IVF_CHECK_LAUNCH();
+  return IVF_OK;
+}
+
+extern "C" int ivf_clstm_set_cam_steps(ivf_clstm_t* n, const int* steps, int n_steps) {
+  IVF_CHECK_ARG(n && steps, "clstm_set_cam_steps: null pointer");
+  IVF_CHECK_ARG(n_steps > 0 && n_steps <= 64 && n_steps <= n->cfg.T, "clstm_set_cam_steps: 1..min(T,64) steps");
+  for (int e = 0; e < n_steps; ++e)
+    IVF_CHECK_ARG(steps[e] >= 0 && steps[e] < n->cfg.T && (e == 0 || steps[e] > steps[e - 1]),
+                  "clstm_set_cam_steps: steps must be increasing inside [0,T)");
+  n->n_cam_steps = n_steps;
+  for (int e = 0; e < n_steps; ++e) n->cam_steps[e] = steps[e];
+  return IVF_OK;
+}
+
+extern "C" int ivf_clstm_layer_buffers(ivf_clstm_t* n, int layer, const float** X, const float** dX, int* hid,
+                                       int* Hp, int* Wp) {
+  IVF_CHECK_ARG(n && n->ws, "clstm_layer_buffers: not bound");
+  IVF_CHECK_ARG(layer >= 0 && layer < (int)n->L.size(), "clstm_layer_buffers: layer %d outside [0,%d)", layer,
+                (int)n->L.size());
+  const LayerPlan& p = n->L[layer];
+  if (X) *X = n->wsf(p.X_off);
+  if (dX) *dX = n->wsf(p.dX_off);
+  if (hid) *hid = n->cfg.hidden;
+  if (Hp) *Hp = p.Hp;
+  if (Wp) *Wp = p.Wp;
+  return IVF_OK;
+}
+
+namespace ivf {
+
+// forward, truncated backward and the reduction; leaves the raw maps [b, st->n, Hp, Wp] at off_cam and the channel
+// weights [b, hid] at off_camw.  layer -1: the stack of the effective steps of the top layer (the reference's
+// branch); 0 .. L-1: every step of that layer.
+static int clstm_cam_core(ivf_clstm* n, const float* x, int b, const int* target, int layer, float* probs,
+                          CamSteps* st, const LayerPlan** lp, hipStream_t s) {
+  const int nl = (int)n->L.size();
+  IVF_CHECK_ARG(x, "clstm_gradcam: null clip");
+  IVF_CHECK_ARG(layer >= -1 && layer < nl, "clstm_gradcam: layer %d outside [-1,%d)", layer, nl);
+  const ivf_clstm_config& c = n->cfg;
+  IVF_PROPAGATE(clstm_run_forward(n, x, b, nullptr, probs, s));
+  if (!target) {          // np.argmax of the output, grad_cam_videos.py:69-70
+    int* t = n->at<int>(n->off_camtgt);
+    IVF_PROPAGATE(ivf_argmax(n->at<float>(n->off_probs), b, c.num_classes, t, s));
+    target = t;
+  }
+  const int li = layer < 0 ? nl - 1 : layer;
+  IVF_PROPAGATE(clstm_run_backward(n, b, target, nullptr, nullptr, nullptr, s, li + 1));
+  const LayerPlan& p = n->L[li];
+  if (layer < 0)
+    IVF_PROPAGATE(cam_steps_from(n->cam_steps, n->n_cam_steps, c.T, st));
+  else
+    IVF_PROPAGATE(cam_steps_from(nullptr, c.T, c.T, st));
+  *lp = &p;
+  return ivf_clstm_gradcam_reduce(n->wsf(p.X_off), n->wsf(p.dX_off), st->s, st->n, n->at<float>(n->off_camw),
+                                  n->at<float>(n->off_cam), b, c.T, c.hidden, p.Hp * p.Wp, s);
+}
+
+}  // namespace ivf
+
+extern "C" int ivf_clstm_gradcam(ivf_clstm_t* n, const float* x, int b, const int* target, int layer, int per_frame,
+                                 int out_h, int out_w, float* cam_out, float* probs, ivf_stream_t stream) {
+  IVF_PROPAGATE(clstm_ready(n, b));
+  IVF_CHECK_ARG(cam_out && out_h > 0 && out_w > 0, "clstm_gradcam: bad args");
+  hipStream_t s = (hipStream_t)stream;
+  CamSteps st;
+  const LayerPlan* p = nullptr;
+  IVF_PROPAGATE(clstm_cam_core(n, x, b, target, layer, probs, &st, &p, s));
+  // step_size = clip_size // maps (grad_cam_videos.py:113): 1 for the per-frame stack of a layer
+  return ivf_cam_resize_normalise(n->at<float>(n->off_cam), cam_out, n->at<float>(n->off_cammm), b, st.n, p->Hp, p->Wp,
+                                  out_h, out_w, n->cfg.T / st.n, per_frame, s);
+}
+
+extern "C" int ivf_clstm_gradcam_raw(ivf_clstm_t* n, const float* x, int b, const int* target, int layer, float* cam,
+                                     float* weights, float* feat, float* grad, float* probs, ivf_stream_t stream) {
+  IVF_PROPAGATE(clstm_ready(n, b));
+  hipStream_t s = (hipStream_t)stream;
+  CamSteps st;
+  const LayerPlan* p = nullptr;
+  IVF_PROPAGATE(clstm_cam_core(n, x, b, target, layer, probs, &st, &p, s));
+  const long plane = (long)p->Hp * p->Wp, row = plane * n->cfg.hidden;
+  if (cam)
+    IVF_CHECK_HIP(hipMemcpyAsync(cam, n->at<float>(n->off_cam), (size_t)b * st.n * plane * 4, hipMemcpyDeviceToDevice, s));
+  if (weights)
+    IVF_CHECK_HIP(hipMemcpyAsync(weights, n->at<float>(n->off_camw), (size_t)b * n->cfg.hidden * 4,
+                                 hipMemcpyDeviceToDevice, s));
+  const float* src[2] = {n->wsf(p->X_off), n->wsf(p->dX_off)};
+  float* dst[2] = {feat, grad};
+  for (int q = 0; q < 2; ++q)
+    if (dst[q]) {
+      const long total = (long)b * st.n * row;
+      hipLaunchKernelGGL(clstm_gather_steps_kernel, dim3(grid_for(total)), dim3(256), 0, s, src[q], st, dst[q], n->cfg.T,
+                         row, total);
+      IVF_CHECK_LAUNCH();
+    }
   return IVF_OK;
 }

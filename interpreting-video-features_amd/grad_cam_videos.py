@@ -6,7 +6,16 @@ from the vendored pytorch-grad-cam/grad-cam.py via `from grad_cam import *`).
 to Mixed_5c, head backward from the (post-softmax) class score, channel-mean
 weights, weighted sum + ReLU, bilinear resize, repeat, min/max normalise
 (csrc/pool_head.hip; reference grad_cam_videos.py:64-142).
+
+`archType="CLSTM"` (models.CLSTM_4.Model, csrc/convlstm.hip) takes two kinds of target layer name:
+`['clstm']` is the reference's branch (grad-cam.py:33-49; the name it tests, `firstCLSTMLayer`, is not an
+attribute of CLSTM_4.Model, whose ConvLSTM module is called `clstm`): the top layer's outputs at the effective
+steps, each map repeated `T // n` times.  `['cell0']`, `['cell1']`, ... is an EXTENSION without a counterpart
+in the reference: that layer's pooled output at every step, with the gradient through the layers above and
+their recurrences, one map per frame.
 """
+import re
+
 import numpy as np
 import torch
 
@@ -27,6 +36,23 @@ def _one_target(target_layers):
     return target_layers[0]
 
 
+def _clstm_layer(model, name):
+    """'clstm' -> None (the reference's stack), 'cell<i>' -> i (per-frame maps of layer i)."""
+    if name == "clstm":
+        return None
+    m = re.fullmatch(r"cell(\d+)", str(name))
+    if m is None or int(m.group(1)) >= model.lstm_layers:
+        raise L.IvfError(f"'{name}' is not a Grad-CAM target of the ConvLSTM: 'clstm' or 'cell0' .. "
+                         f"'cell{model.lstm_layers - 1}'")
+    return int(m.group(1))
+
+
+def _arch(archType):
+    if archType not in ("I3D", "CLSTM"):
+        raise L.IvfError(f"archType must be 'I3D' or 'CLSTM', got {archType!r}")
+    return archType
+
+
 class FeatureExtractor():
     """pytorch-grad-cam/grad-cam.py:11-54: activations of the target layers and the
     output of the last feature module.  Gradients are produced by the HIP head
@@ -42,12 +68,16 @@ class FeatureExtractor():
         self.gradients.append(grad)
 
     def __call__(self, x):
-        if self.archType != "I3D":
-            raise L.IvfError("FeatureExtractor: only archType 'I3D' is built; the reference's CLSTM branch "
-                             "refers to attributes CLSTM_4.Model does not have (SURVEY.md F5)")
-        _one_target(self.target_layers)
+        _arch(self.archType)
+        name = _one_target(self.target_layers)
         self.gradients = []
         eng = self.model._engine_for(x)
+        if self.archType == "CLSTM":
+            # torch.stack(x[0]) of grad-cam.py:43-49: [n, B, hid, h, w]; the gradient of the predicted class's
+            # score with respect to it is kept where the reference's hook would put it
+            raw = eng.gradcam_raw(x, None, layer=_clstm_layer(self.model, name))
+            self.gradients = [raw["grad"].transpose(0, 1).contiguous()]
+            return [raw["feat"].transpose(0, 1).contiguous()], raw["probs"]
         eng.forward(x)
         acts = [eng.endpoint(t, x.shape[0]) for t in self.target_layers]
         return acts, eng.endpoint('Mixed_5c', x.shape[0])
@@ -78,6 +108,8 @@ class ModelOutputsVideo(ModelOutputs):
 
     def __call__(self, x):
         target_activations, feat = self.feature_extractor(x)
+        if self.archType == "CLSTM":     # the model's own output, grad_cam_videos.py:27-43
+            return target_activations, feat
         eng = self.model._engine_for(x)
         output = eng.forward(x)          # head of grad_cam_videos.py:30-41 (avg-pool, logits, softmax)
         return target_activations, output
@@ -120,9 +152,10 @@ class GradCamVideo(GradCam):
         self.extractor = ModelOutputsVideo(self.model, target_layer_names, self.archType)
 
     def __call__(self, input, index=None):
-        if self.archType != "I3D":
-            raise L.IvfError("GradCamVideo: only archType 'I3D' is built (SURVEY.md F5)")
+        _arch(self.archType)
         layer = _one_target(self.extractor.feature_extractor.target_layers)
+        if self.archType == "CLSTM":
+            layer = _clstm_layer(self.model, layer)
         x = input.cuda() if self.cuda else input
         L.require_gpu(x)
         if x.shape[0] != 1:

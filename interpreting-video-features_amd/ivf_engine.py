@@ -300,7 +300,9 @@ class CLSTMEngine:
     convolution_lstm.py:96-132) on `max_batch` clips [C,T,H,W]."""
 
     def __init__(self, num_classes, clip_shape, max_batch=1, hidden=4, layers=2, kernel=5, stride=2,
-                 softmax=False, batch_norm=True, out_step=None, out_steps=None, device=None):
+                 softmax=False, batch_norm=True, out_step=None, out_steps=None, device=None, effective_steps=None):
+        """effective_steps: the effective steps inside the clip (convolution_lstm.py:129-130), whose top-layer
+        outputs are the map stack of Grad-CAM target 'clstm'; default: the steps that feed endFC."""
         L.require_gpu()
         self.device = torch.device(device if device is not None else "cuda")
         C, T, H, W = clip_shape
@@ -329,6 +331,11 @@ class CLSTMEngine:
             self._weights = _arena(L.lib().ivf_clstm_weights_bytes(self._h), self.device)
             self._ws = _arena(L.lib().ivf_clstm_workspace_bytes(self._h), self.device)
         L.check(L.lib().ivf_clstm_bind(self._h, L.ptr(self._weights), L.ptr(self._ws)))
+        if effective_steps is None:
+            effective_steps = list(out_steps) if out_steps is not None else [cfg.out_step]
+        self.effective_steps = tuple(int(v) for v in effective_steps)
+        L.check(L.lib().ivf_clstm_set_cam_steps(self._h, (c_int * len(self.effective_steps))(*self.effective_steps),
+                                                len(self.effective_steps)))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -418,10 +425,73 @@ class CLSTMEngine:
         """I3DEngine.blob_scores with the ConvLSTM backbone (ivf_clstm_blob_scores)."""
         return _blob_scores(self, L.lib().ivf_clstm_blob_scores, x, target, max_len, mode)
 
-    def gradcam(self, *a, **kw):
-        raise L.IvfError("Grad-CAM for the PyTorch ConvLSTM cannot run in the reference either "
-                         "(grad-cam.py:33-49 refers to attributes CLSTM_4.Model lacks, SURVEY.md F5); "
-                         "not built")
+    # ------------------------------------------------------------ Grad-CAM
+    def _cam_layer(self, layer):
+        """layer None -> -1 (the reference's stack of effective steps), int i -> per-frame maps of layer i."""
+        if layer is None:
+            return -1, len(self.effective_steps)
+        if isinstance(layer, bool) or not isinstance(layer, (int, np.integer)) or not 0 <= int(layer) < self.layers:
+            raise L.IvfError(f"Grad-CAM layer must be None or an int in [0,{self.layers}), got {layer!r}")
+        return int(layer), self.clip_shape[1]
+
+    def layer_dims(self, layer):
+        """(hid, Hp, Wp) of a layer's pooled output."""
+        v = [c_int() for _ in range(3)]
+        L.check(L.lib().ivf_clstm_layer_buffers(self._h, int(layer), None, None, *[byref(a) for a in v]))
+        return tuple(a.value for a in v)
+
+    def layer_state(self, layer, b):
+        """Copies of what the last forward / backward left for a layer: pooled outputs and their gradient,
+        both [b,T,hid,Hp,Wp]."""
+        X, dX = c_void_p(), c_void_p()
+        L.check(L.lib().ivf_clstm_layer_buffers(self._h, int(layer), byref(X), byref(dX), None, None, None))
+        hid, Hp, Wp = self.layer_dims(layer)
+        T = self.clip_shape[1]
+        n = b * T * hid * Hp * Wp
+        out = []
+        for p in (X, dX):
+            off = p.value - self._ws.data_ptr()
+            out.append(self._ws[off:off + 4 * n].view(torch.float32).view(b, T, hid, Hp, Wp).clone())
+        return tuple(out)
+
+    def gradcam(self, x, target=None, per_frame=True, out_hw=None, layer=None):
+        """GradCamVideo for b clips: (cam [b,frames,H,W], probs [b,K]), the I3D engine's convention.
+
+        layer=None is the reference's CLSTM branch (grad-cam.py:33-49, grad_cam_videos.py:88-142): the top layer's
+        pooled outputs at the effective steps with the gradient endFC sends into them, n_eff maps each repeated
+        T // n_eff times.  layer=i is an EXTENSION (no counterpart in the reference, pinned by autograd on the
+        reference's model): layer i's pooled output at every step with the gradient of the class score through
+        the layers above and their recurrences; T per-frame maps that line up with the temporal mask."""
+        x = self._clip(x)
+        b = x.shape[0]
+        C, T, H, W = self.clip_shape
+        oh, ow = out_hw if out_hw is not None else (H, W)
+        li, n = self._cam_layer(layer)
+        tgt = self._targets(target, b) if target is not None else None     # None: argmax on the device
+        cam = torch.empty(b, n * (T // n), oh, ow, device=self.device)
+        probs = torch.empty(b, self.K, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().ivf_clstm_gradcam(self._h, L.ptr(x), b, L.ptr(tgt), li, 1 if per_frame else 0, int(oh),
+                                              int(ow), L.ptr(cam), L.ptr(probs), L.stream()))
+        return cam, probs
+
+    def gradcam_raw(self, x, target=None, layer=None):
+        """The pieces of `gradcam` before the resize: dict of cam [b,n,Hp,Wp], weights [b,hid], feat and grad
+        [b,n,hid,Hp,Wp] (the features and gradients the reduction read) and probs [b,K]."""
+        x = self._clip(x)
+        b = x.shape[0]
+        li, n = self._cam_layer(layer)
+        hid, Hp, Wp = self.layer_dims(self.layers - 1 if li < 0 else li)
+        tgt = self._targets(target, b) if target is not None else None
+        dev = self.device
+        out = dict(cam=torch.empty(b, n, Hp, Wp, device=dev), weights=torch.empty(b, hid, device=dev),
+                   feat=torch.empty(b, n, hid, Hp, Wp, device=dev), grad=torch.empty(b, n, hid, Hp, Wp, device=dev),
+                   probs=torch.empty(b, self.K, device=dev))
+        with torch.cuda.device(dev):
+            L.check(L.lib().ivf_clstm_gradcam_raw(self._h, L.ptr(x), b, L.ptr(tgt), li, L.ptr(out["cam"]),
+                                                  L.ptr(out["weights"]), L.ptr(out["feat"]), L.ptr(out["grad"]),
+                                                  L.ptr(out["probs"]), L.stream()))
+        return out
 
 
 class TFCLSTMEngine:

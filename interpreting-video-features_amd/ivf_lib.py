@@ -158,6 +158,11 @@ _SIGS_OPT = {
     "ivf_clstm_search": (c_int, [_P, _P, _I, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _I, _I, _I, _P, _P]),
     "ivf_clstm_perturbed_forward": (c_int, [_P, _P, _I, _P, _I, _P, _P]),
     "ivf_clstm_blob_scores": (c_int, [_P, _P, _I, _P, _I, _I, _P, _P]),
+    "ivf_clstm_gradcam_reduce": (c_int, [_P, _P, POINTER(c_int), _I, _P, _P, _I, _I, _I, _I, _P]),
+    "ivf_clstm_set_cam_steps": (c_int, [_P, POINTER(c_int), _I]),
+    "ivf_clstm_gradcam": (c_int, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "ivf_clstm_gradcam_raw": (c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "ivf_clstm_layer_buffers": (c_int, [_P, _I, POINTER(c_void_p), POINTER(c_void_p)] + [POINTER(c_int)] * 3),
     # csrc/tf_clstm.hip (documented extension)
     "ivf_tfclstm_create": (c_int, [POINTER(TFCLSTMConfig), POINTER(c_void_p)]),
     "ivf_tfclstm_destroy": (None, [_P]),

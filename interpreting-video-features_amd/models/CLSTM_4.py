@@ -122,7 +122,9 @@ class Model(torch.nn.Module):
                                          batch_norm=bool(self.batch_normalization),
                                          out_step=self._out_step(),
                                          out_steps=self._out_steps() if self.use_entire_seq else None,
-                                         device=x.device)
+                                         device=x.device,
+                                         effective_steps=sorted({s for s in self.effective_step
+                                                                 if 0 <= s < self.step}))
             ent = [-1, eng]
             self._engine_cache[key] = ent
         if ent[0] != self._weights_version:
