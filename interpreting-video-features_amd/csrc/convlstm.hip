@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "ivf_common.h"
+#include "search_driver.h"
 
 namespace ivf {
 
@@ -944,11 +945,6 @@ __global__ void clstm_gather_steps_kernel(const float* __restrict__ src, CamStep
   }
 }
 
-static inline int grid_for(long total, int block = 256, int cap = 4096) {
-  long g = (total + block - 1) / block;
-  return (int)(g > cap ? cap : (g ? g : 1));
-}
-
 struct LayerPlan {
   int cin, Hin, Win, Ho, Wo, Hp, Wp;
   size_t wx_off, bx_off, wh_off;                    // floats in weights arena (raw reference layout)
@@ -969,8 +965,8 @@ struct ivf_clstm {
   int feat;      // hid * Hp * Wp of the top layer
   int fc_in;     // endFC inputs: feat * number of output steps
   size_t ws_bytes;
-  size_t off_p, off_dp, off_flat, off_dflat, off_logits, off_probs, off_score, off_sig, off_terms, off_dreg,
-      off_dsig, off_fbwd, off_pair, off_cam, off_camw, off_cammm, off_camtgt;
+  size_t off_p, off_dp, off_flat, off_dflat, off_logits, off_probs, off_cam, off_camw, off_cammm, off_camtgt;
+  SearchScratch sc;
   int n_cam_steps = 0;      // effective steps reached: the map stack of Grad-CAM target 'clstm'
   int cam_steps[64];
   float* wa = nullptr;
@@ -1065,13 +1061,8 @@ extern "C" int ivf_clstm_create(const ivf_clstm_config* c, ivf_clstm_t** out) {
   const int K = c->num_classes;
   n->off_logits = takeb(B * K * 4);
   n->off_probs = takeb(B * K * 4);
-  n->off_score = takeb(B * 4);
-  n->off_sig = takeb(B * T * 4);
-  n->off_terms = takeb(B * 2 * 4);
-  n->off_dreg = takeb(B * T * 4);
-  n->off_dsig = takeb(B * T * 4);
-  n->off_fbwd = takeb(ivf_freeze_bwd_workspace_bytes((int)B, (int)T));
-  n->off_pair = takeb(B * T * 8);
+  n->sc.carve(takeb, B, T);
+  n->sc.carve_pairs(takeb, B, T, 8);
   // Grad-CAM: raw maps of the largest pooled plane (layer 0) at every step, channel weights, min/max of the resize
   n->off_cam = takeb(B * T * n->L[0].Hp * n->L[0].Wp * 4);
   n->off_camw = takeb(B * hid * 4);
@@ -1372,6 +1363,29 @@ static int clstm_run_backward(ivf_clstm* n, int b, const int* target, const floa
   return IVF_OK;
 }
 
+// the plan as the shared search driver sees it: candidates are staged NCTHW in P, their gradient lands in dP
+static Backbone backbone(ivf_clstm* n) {
+  const ivf_clstm_config& c = n->cfg;
+  Backbone v{};
+  v.plan = n;
+  v.B = c.B; v.C = c.C; v.T = c.T; v.HW = c.H * c.W; v.K = c.num_classes;
+  v.layout = 0;
+  v.in = n->at<float>(n->off_p);
+  v.din = n->at<float>(n->off_dp);
+  v.probs = n->at<float>(n->off_probs);
+  v.ws = n->ws;
+  v.sc = &n->sc;
+  v.forward = [](void* p, int b, float* probs, hipStream_t s) {
+    ivf_clstm* n = (ivf_clstm*)p;
+    return clstm_run_forward(n, n->at<float>(n->off_p), b, nullptr, probs, s);
+  };
+  v.backward = [](void* p, int b, const int* target, float* score, hipStream_t s) {
+    ivf_clstm* n = (ivf_clstm*)p;
+    return clstm_run_backward(n, b, target, nullptr, score, n->at<float>(n->off_dp), s);
+  };
+  return v;
+}
+
 }  // namespace ivf
 
 extern "C" int ivf_clstm_forward(ivf_clstm_t* n, const float* x, int b, float* logits, float* probs,
@@ -1396,55 +1410,15 @@ extern "C" int ivf_clstm_search(ivf_clstm_t* n, const float* x, int b, const int
   IVF_CHECK_ARG(x && target && raw_mask && exp_avg && exp_avg_sq, "clstm_search: null pointer");
   IVF_CHECK_ARG(N >= 0 && first_step >= 1, "clstm_search: bad iteration counts");
   IVF_CHECK_ARG(mode == 0 || mode == 1, "clstm_search: mode must be 0 (freeze) or 1 (reverse)");
-  const ivf_clstm_config& c = n->cfg;
-  hipStream_t s = (hipStream_t)stream;
-  const int T = c.T, HW = c.H * c.W;
-  float* sig = n->at<float>(n->off_sig);
-  float* terms = n->at<float>(n->off_terms);
-  float* dreg = n->at<float>(n->off_dreg);
-  float* dsig = n->at<float>(n->off_dsig);
-  float* score = n->at<float>(n->off_score);
-  float* P = n->at<float>(n->off_p);
-  float* dP = n->at<float>(n->off_dp);
-  int* partner = n->at<int>(n->off_pair);
-  float* weight = (float*)(partner + (size_t)c.B * c.T);
-  for (int it = 0; it < N; ++it) {
-    IVF_PROPAGATE(ivf_mask_reg(raw_mask, b, T, lam1, lam2, sig, terms, dreg, s));
-    if (mode == 0) {
-      IVF_PROPAGATE(ivf_freeze_fwd(x, sig, P, b, c.C, T, HW, 1, 0, s));
-    } else {
-      IVF_PROPAGATE(ivf_submask_pairs_batched(sig, b, T, 0.1f, partner, weight, s));
-      IVF_PROPAGATE(ivf_reverse_fwd_batched(x, partner, weight, P, b, c.C, T, HW, 0, s));
-    }
-    IVF_PROPAGATE(clstm_run_forward(n, P, b, nullptr, nullptr, s));
-    IVF_PROPAGATE(clstm_run_backward(n, b, target, nullptr, score, dP, s));
-    if (mode == 0)
-      IVF_PROPAGATE(ivf_freeze_bwd(x, sig, dP, dsig, nullptr, b, c.C, T, HW, 1, 0, n->at<void>(n->off_fbwd), s));
-    else
-      IVF_PROPAGATE(ivf_reverse_bwd(x, partner, dP, dsig, b, c.C, T, HW, 0, n->at<void>(n->off_fbwd), s));
-    IVF_PROPAGATE(ivf_search_step(raw_mask, sig, dsig, dreg, terms, score, exp_avg, exp_avg_sq,
-                                  traj ? traj + (size_t)it * b * 4 : nullptr, b, T, first_step + it, lr, beta1,
-                                  beta2, eps, s));
-  }
-  return IVF_OK;
+  return run_search(backbone(n), x, b, target, raw_mask, exp_avg, exp_avg_sq, lam1, lam2, lr, beta1, beta2,
+                    [eps](int) { return eps; }, N, first_step, mode, traj, (hipStream_t)stream);
 }
 
 extern "C" int ivf_clstm_perturbed_forward(ivf_clstm_t* n, const float* x, int b, const float* mask, int mode,
                                            float* probs, ivf_stream_t stream) {
   IVF_PROPAGATE(clstm_ready(n, b));
   IVF_CHECK_ARG(x && mask && (mode == 0 || mode == 1), "clstm_perturbed_forward: bad args");
-  const ivf_clstm_config& c = n->cfg;
-  hipStream_t s = (hipStream_t)stream;
-  float* P = n->at<float>(n->off_p);
-  if (mode == 0) {
-    IVF_PROPAGATE(ivf_freeze_fwd(x, mask, P, b, c.C, c.T, c.H * c.W, 1, 0, s));
-  } else {
-    int* partner = n->at<int>(n->off_pair);
-    float* weight = (float*)(partner + (size_t)c.B * c.T);
-    IVF_PROPAGATE(ivf_submask_pairs_batched(mask, b, c.T, 0.1f, partner, weight, s));
-    IVF_PROPAGATE(ivf_reverse_fwd_batched(x, partner, weight, P, b, c.C, c.T, c.H * c.W, 0, s));
-  }
-  return clstm_run_forward(n, P, b, nullptr, probs, s);
+  return run_perturbed_forward(backbone(n), x, mask, b, mode, probs, (hipStream_t)stream);
 }
 
 // Exhaustive one-blob search (maskType 'combi'), as ivf_i3d_blob_scores: candidates staged into the NCTHW buffer P.
@@ -1454,19 +1428,7 @@ extern "C" int ivf_clstm_blob_scores(ivf_clstm_t* n, const float* x, int b, cons
   IVF_CHECK_ARG(x && target && scores, "clstm_blob_scores: null pointer");
   IVF_CHECK_ARG(b > 0, "clstm_blob_scores: bad batch %d", b);
   IVF_CHECK_ARG(mode == 0 || mode == 1, "clstm_blob_scores: mode must be 0 (freeze) or 1 (reverse)");
-  const ivf_clstm_config& c = n->cfg;
-  const int nc = ivf_blob_count(c.T, max_len);
-  if (nc < 0) return IVF_ERR_BAD_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  float* P = n->at<float>(n->off_p);
-  const long long total = (long long)b * nc;
-  for (long long first = 0; first < total; first += c.B) {
-    const int cnt = (int)std::min<long long>(c.B, total - first);
-    IVF_PROPAGATE(ivf_blob_stage(x, b, c.C, c.T, c.H * c.W, max_len, mode, first, cnt, P, 0, s));
-    IVF_PROPAGATE(clstm_run_forward(n, P, cnt, nullptr, nullptr, s));
-    IVF_PROPAGATE(blob_pick(n->at<float>(n->off_probs), target, c.num_classes, nc, first, cnt, scores, s));
-  }
-  return IVF_OK;
+  return run_blob_scores(backbone(n), x, b, target, max_len, mode, scores, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- Grad-CAM (grad_cam_videos.py:64-142, archType "CLSTM")

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "ivf_common.h"
+#include "search_driver.h"
 
 namespace ivf {
 
@@ -93,8 +94,8 @@ struct ivf_i3d {
   size_t weights_floats = 0;
   size_t ws_bytes = 0;
   // misc workspace offsets (bytes)
-  size_t off_logits, off_probs, off_pooled, off_dpooled, off_score, off_sig, off_terms, off_dreg, off_dsig,
-      off_fbwd, off_target, off_cam, off_camw, off_mm, off_dfeat_raw, off_pair;
+  size_t off_logits, off_probs, off_pooled, off_dpooled, off_target, off_cam, off_camw, off_mm, off_dfeat_raw;
+  SearchScratch sc;
   float* warena = nullptr;
   char* ws = nullptr;
   std::vector<bool> loaded;
@@ -367,12 +368,7 @@ static int build_plan(ivf_i3d* n) {
   n->off_probs = takeb(B * K * 4);
   n->off_pooled = takeb(B * 1024 * 4);
   n->off_dpooled = takeb(B * 1024 * 4);
-  n->off_score = takeb(B * 4);
-  n->off_sig = takeb(B * T * 4);
-  n->off_terms = takeb(B * 2 * 4);
-  n->off_dreg = takeb(B * T * 4);
-  n->off_dsig = takeb(B * T * 4);
-  n->off_fbwd = takeb(ivf_freeze_bwd_workspace_bytes((int)B, T));
+  n->sc.carve(takeb, B, T);
   n->off_target = takeb(B * 4);
   size_t max_pos = 0, max_t = 0;      // Grad-CAM on any endpoint (ivf_i3d_gradcam_layer)
   for (const auto& bf : n->bufs) {
@@ -384,7 +380,7 @@ static int build_plan(ivf_i3d* n) {
   n->off_camw = takeb(B * 1024 * 4);
   n->off_mm = takeb(B * max_t * 2 * 4);
   n->off_dfeat_raw = takeb(B * f.per_clip() * 4);
-  n->off_pair = takeb(B * T * 12);
+  n->sc.carve_pairs(takeb, B, T, 12);
   n->ws_bytes = bytes;
   n->loaded.assign(n->convs.size(), false);
   return IVF_OK;
@@ -559,9 +555,8 @@ static int run_forward(ivf_i3d* n, int b, float* logits, float* probs, hipStream
   const ConvLayer& L = n->convs.back();
   float* lg = n->at<float>(n->off_logits);
   float* pr = n->at<float>(n->off_probs);
-  IVF_PROPAGATE((n->act16() ? ivf_head_fwd_bf16 : (decltype(&ivf_head_fwd_bf16))ivf_head_fwd)(
-      n->act(n->feat_buf), n->warena + L.wf_off, n->warena + L.shift_off, n->at<float>(n->off_pooled), lg, pr, b,
-      f.T * f.H * f.W, f.C, n->cfg.num_classes, n->cfg.softmax, s));
+  IVF_PROPAGATE(head_fwd(n->act(n->feat_buf), n->act16(), n->warena + L.wf_off, n->warena + L.shift_off,
+                         n->at<float>(n->off_pooled), lg, pr, b, f.T * f.H * f.W, f.C, n->cfg.num_classes, n->cfg.softmax, s));
   size_t nb = (size_t)b * n->cfg.num_classes * sizeof(float);
   if (logits) IVF_CHECK_HIP(hipMemcpyAsync(logits, lg, nb, hipMemcpyDeviceToDevice, s));
   if (probs) IVF_CHECK_HIP(hipMemcpyAsync(probs, pr, nb, hipMemcpyDeviceToDevice, s));
@@ -573,9 +568,9 @@ static int run_backward(ivf_i3d* n, int b, const int* target, const float* dout,
                         hipStream_t s) {
   const ActBuf& f = n->bufs[n->feat_buf];
   const ConvLayer& Lh = n->convs.back();
-  IVF_PROPAGATE((n->act16() ? ivf_head_bwd_bf16 : (decltype(&ivf_head_bwd_bf16))ivf_head_bwd)(
-      n->act(n->feat_buf), n->warena + Lh.wf_off, n->at<float>(n->off_probs), target, dout, score, nullptr,
-      n->grad(n->feat_buf), b, f.T * f.H * f.W, f.C, n->cfg.num_classes, n->cfg.softmax, 1, s));
+  IVF_PROPAGATE(head_bwd(n->act(n->feat_buf), n->act16(), n->warena + Lh.wf_off, n->at<float>(n->off_probs), target, dout,
+                         score, nullptr, n->grad(n->feat_buf), b, f.T * f.H * f.W, f.C, n->cfg.num_classes, n->cfg.softmax,
+                         1, s));
   SideLane lane(n, s);
   IVF_PROPAGATE(lane.rc);
   int module = -1;
@@ -650,9 +645,23 @@ __global__ void cl4_to_ncthw_kernel(const float* __restrict__ y, float* __restri
   }
 }
 
-static inline int grid_for(size_t total, int block = 256, int cap = 4096) {
-  size_t g = (total + block - 1) / block;
-  return (int)(g > (size_t)cap ? cap : (g ? g : 1));
+// the plan as the shared search driver sees it: candidates are staged as 16-byte channels-last pixels in act(0)
+static Backbone backbone(ivf_i3d* n) {
+  const ivf_i3d_config& c = n->cfg;
+  Backbone v{};
+  v.plan = n;
+  v.B = c.B; v.C = c.C; v.T = c.T; v.HW = c.H * c.W; v.K = c.num_classes;
+  v.layout = 4;
+  v.in = n->act(0);
+  v.din = n->grad(0);
+  v.probs = n->at<float>(n->off_probs);
+  v.ws = n->ws;
+  v.sc = &n->sc;
+  v.forward = [](void* p, int b, float* probs, hipStream_t s) { return run_forward((ivf_i3d*)p, b, nullptr, probs, s); };
+  v.backward = [](void* p, int b, const int* target, float* score, hipStream_t s) {
+    return run_backward((ivf_i3d*)p, b, target, nullptr, score, s);
+  };
+  return v;
 }
 
 }  // namespace ivf
@@ -828,79 +837,25 @@ extern "C" int ivf_i3d_search(ivf_i3d_t* net, const float* x, int b, const int* 
   IVF_CHECK_ARG(x && target && raw_mask && exp_avg && exp_avg_sq, "i3d_search: null pointer");
   IVF_CHECK_ARG(N >= 0 && first_step >= 1, "i3d_search: bad iteration counts");
   IVF_CHECK_ARG(mode == 0 || mode == 1, "i3d_search: mode must be 0 (freeze) or 1 (reverse)");
-  const ivf_i3d_config& c = net->cfg;
-  hipStream_t s = (hipStream_t)stream;
-  const int T = c.T, HW = c.H * c.W;
-  float* sig = net->at<float>(net->off_sig);
-  float* terms = net->at<float>(net->off_terms);
-  float* dreg = net->at<float>(net->off_dreg);
-  float* dsig = net->at<float>(net->off_dsig);
-  float* score = net->at<float>(net->off_score);
-  int* partner = net->at<int>(net->off_pair);
-  float* weight = (float*)(partner + (size_t)c.B * c.T);
-  for (int it = 0; it < N; ++it) {
-    prof_set_iteration(it);
-    IVF_PROPAGATE(ivf_mask_reg(raw_mask, b, T, lam1, lam2, sig, terms, dreg, s));              // smth:198-200
-    if (mode == 0) {
-      IVF_PROPAGATE(ivf_freeze_fwd(x, sig, net->act(0), b, c.C, T, HW, 1, 4, s));              // smth:202
-    } else {
-      IVF_PROPAGATE(ivf_submask_pairs_batched(sig, b, T, 0.1f, partner, weight, s));
-      IVF_PROPAGATE(ivf_reverse_fwd_batched(x, partner, weight, net->act(0), b, c.C, T, HW, 4, s));
-    }
-    IVF_PROPAGATE(run_forward(net, b, nullptr, nullptr, s));                                    // smth:202-205
-    IVF_PROPAGATE(run_backward(net, b, target, nullptr, score, s));                             // smth:213
-    if (mode == 0)
-      IVF_PROPAGATE(ivf_freeze_bwd(x, sig, net->grad(0), dsig, nullptr, b, c.C, T, HW, 1, 4,
-                                   net->at<void>(net->off_fbwd), s));
-    else
-      IVF_PROPAGATE(ivf_reverse_bwd(x, partner, net->grad(0), dsig, b, c.C, T, HW, 4,
-                                    net->at<void>(net->off_fbwd), s));
-    IVF_PROPAGATE(ivf_search_step(raw_mask, sig, dsig, dreg, terms, score, exp_avg, exp_avg_sq,
-                                  traj ? traj + (size_t)it * b * 4 : nullptr, b, T, first_step + it, lr,
-                                  beta1, beta2, eps, s));                                       // smth:207-214
-  }
-  prof_set_iteration(-1);   // sampling off outside the loop
-  return IVF_OK;
+  return run_search(backbone(net), x, b, target, raw_mask, exp_avg, exp_avg_sq, lam1, lam2, lr, beta1, beta2,
+                    [eps](int) { return eps; }, N, first_step, mode, traj, (hipStream_t)stream);
 }
 
 extern "C" int ivf_i3d_perturbed_forward(ivf_i3d_t* net, const float* x, int b, const float* mask, int mode,
                                          float* probs, ivf_stream_t stream) {
   IVF_PROPAGATE(check_ready(net, b));
   IVF_CHECK_ARG(x && mask && (mode == 0 || mode == 1), "i3d_perturbed_forward: bad args");
-  const ivf_i3d_config& c = net->cfg;
-  hipStream_t s = (hipStream_t)stream;
-  if (mode == 0) {
-    IVF_PROPAGATE(ivf_freeze_fwd(x, mask, net->act(0), b, c.C, c.T, c.H * c.W, 1, 4, s));
-  } else {
-    int* partner = net->at<int>(net->off_pair);
-    float* weight = (float*)(partner + (size_t)c.B * c.T);
-    IVF_PROPAGATE(ivf_submask_pairs_batched(mask, b, c.T, 0.1f, partner, weight, s));
-    IVF_PROPAGATE(ivf_reverse_fwd_batched(x, partner, weight, net->act(0), b, c.C, c.T, c.H * c.W, 4, s));
-  }
-  return run_forward(net, b, nullptr, probs, s);
+  return run_perturbed_forward(backbone(net), x, mask, b, mode, probs, (hipStream_t)stream);
 }
 
-// Exhaustive one-blob search (maskType 'combi'): the b*n candidates of b clips run in chunks of the plan's B rows --
-// stage straight into the input buffer, forward, pick the target score -- all on one stream, no host sync, no
-// allocation.  Chunks cross clip boundaries, so one clip still fills the plan.
+// Exhaustive one-blob search (maskType 'combi'): run_blob_scores, candidates staged straight into the input buffer.
 extern "C" int ivf_i3d_blob_scores(ivf_i3d_t* net, const float* x, int b, const int* target, int max_len, int mode,
                                    float* scores, ivf_stream_t stream) {
   IVF_PROPAGATE(check_ready(net, 1));
   IVF_CHECK_ARG(x && target && scores, "i3d_blob_scores: null pointer");
   IVF_CHECK_ARG(b > 0, "i3d_blob_scores: bad batch %d", b);
   IVF_CHECK_ARG(mode == 0 || mode == 1, "i3d_blob_scores: mode must be 0 (freeze) or 1 (reverse)");
-  const ivf_i3d_config& c = net->cfg;
-  const int n = ivf_blob_count(c.T, max_len);
-  if (n < 0) return IVF_ERR_BAD_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const long long total = (long long)b * n;
-  for (long long first = 0; first < total; first += c.B) {
-    const int cnt = (int)std::min<long long>(c.B, total - first);
-    IVF_PROPAGATE(ivf_blob_stage(x, b, c.C, c.T, c.H * c.W, max_len, mode, first, cnt, net->act(0), 4, s));
-    IVF_PROPAGATE(run_forward(net, cnt, nullptr, nullptr, s));
-    IVF_PROPAGATE(blob_pick(net->at<float>(net->off_probs), target, c.num_classes, n, first, cnt, scores, s));
-  }
-  return IVF_OK;
+  return run_blob_scores(backbone(net), x, b, target, max_len, mode, scores, (hipStream_t)stream);
 }
 
 extern "C" int ivf_i3d_gradcam(ivf_i3d_t* net, const float* x, int b, const int* target, int per_frame,
@@ -916,13 +871,11 @@ extern "C" int ivf_i3d_gradcam(ivf_i3d_t* net, const float* x, int b, const int*
   float* draw = net->at<float>(net->off_dfeat_raw);
   // gradient of the (post-softmax) class score w.r.t. Mixed_5c, ungated (the hook of
   // pytorch-grad-cam/grad-cam.py:50-51 sees the raw gradient)
-  IVF_PROPAGATE((net->act16() ? ivf_head_bwd_bf16 : (decltype(&ivf_head_bwd_bf16))ivf_head_bwd)(
-      net->act(net->feat_buf), net->warena + Lh.wf_off, net->at<float>(net->off_probs), target, nullptr, nullptr, nullptr,
-      draw, b, npos, f.C, c.num_classes, c.softmax, 0, s));
+  IVF_PROPAGATE(head_bwd(net->act(net->feat_buf), net->act16(), net->warena + Lh.wf_off, net->at<float>(net->off_probs),
+                         target, nullptr, nullptr, nullptr, draw, b, npos, f.C, c.num_classes, c.softmax, 0, s));
   float* wts = net->at<float>(net->off_camw);
   float* cm = net->at<float>(net->off_cam);
-  IVF_PROPAGATE((net->act16() ? ivf_gradcam_reduce_bf16 : (decltype(&ivf_gradcam_reduce_bf16))ivf_gradcam_reduce)(
-      net->act(net->feat_buf), draw, wts, cm, b, npos, f.C, s));
+  IVF_PROPAGATE(gradcam_reduce(net->act(net->feat_buf), draw, net->act16(), wts, cm, b, npos, f.C, s));
   IVF_CHECK_ARG(c.T / f.T >= 1, "i3d_gradcam: clip shorter than the feature map");
   return ivf_cam_resize_normalise(cm, cam, net->at<float>(net->off_mm), b, f.T, f.H, f.W, out_h, out_w,
                                   c.T / f.T, per_frame, s);
@@ -953,8 +906,7 @@ extern "C" int ivf_i3d_gradcam_layer(ivf_i3d_t* net, const float* x, int b, cons
   const int npos = t.T * t.H * t.W;
   float* wts = net->at<float>(net->off_camw);
   float* cm = net->at<float>(net->off_cam);
-  IVF_PROPAGATE((net->act16() ? ivf_gradcam_reduce_bf16 : (decltype(&ivf_gradcam_reduce_bf16))ivf_gradcam_reduce)(
-      net->act(X), net->grad(X), wts, cm, b, npos, t.C, s));
+  IVF_PROPAGATE(gradcam_reduce(net->act(X), net->grad(X), net->act16(), wts, cm, b, npos, t.C, s));
   return ivf_cam_resize_normalise(cm, cam, net->at<float>(net->off_mm), b, t.T, t.H, t.W, out_h, out_w, c.T / t.T,
                                   per_frame, s);
 }

@@ -23,6 +23,16 @@ void prof_name(int variant, const char* fmt, ...);   // kernel name of a profile
 int blob_pick(const float* probs, const int* target, int K, int n, long long first, int count, float* scores,
               hipStream_t s);
 
+// classification head and Grad-CAM reduction (pool_head.hip) on activations / gradients stored as fp32, or as bf16 when
+// `bf16` is set: what ivf_head_fwd{,_bf16}, ivf_head_bwd{,_bf16} and ivf_gradcam_reduce{,_bf16} do, storage type at run time
+int head_fwd(const void* feat, bool bf16, const float* w, const float* bias, float* pooled, float* logits, float* probs,
+             int B, int npos, int C, int K, int softmax, hipStream_t s);
+int head_bwd(const void* feat, bool bf16, const float* w, const float* probs, const int* target, const float* dout,
+             float* score, float* dpooled, void* dfeat, int B, int npos, int C, int K, int softmax, int gate_relu,
+             hipStream_t s);
+int gradcam_reduce(const void* feat, const void* grad, bool bf16, float* weights, float* cam, int B, int npos, int C,
+                   hipStream_t s);
+
 #define IVF_CHECK_ARG(cond, ...)                 \
   do {                                           \
     if (!(cond)) {                               \
@@ -62,6 +72,11 @@ static inline int raise_lds_limit(const void* kernel, int bytes, LdsAttrOnce& on
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// blocks of a grid-stride launch over `total` elements: at least 1, at most `cap`
+static inline int grid_for(size_t total, int block = 256, int cap = 4096) {
+  size_t g = (total + block - 1) / block;
+  return (int)(g > (size_t)cap ? cap : (g ? g : 1));
+}
 
 // TF-'same' front padding along one dim (reference I3D_doubled.py:9-13, 29-34).
 static inline void same_pad(int n, int k, int s, int* front, int* back) {

@@ -493,11 +493,6 @@ __global__ void sigmoid_kernel(const float* __restrict__ x, float* __restrict__ 
   if (i < n) y[i] = 1.f / (1.f + expf(-x[i]));
 }
 
-static inline int grid_for(size_t total, int block = 256, int cap = 2048) {
-  size_t g = (total + block - 1) / block;
-  return (int)(g > (size_t)cap ? cap : (g ? g : 1));
-}
-
 constexpr int FREEZE_BWD_BLOCKS_PER_CLIP = 64;
 
 }  // namespace ivf
@@ -511,15 +506,15 @@ extern "C" int ivf_freeze_fwd(const float* x, const float* mask, float* p, int B
   IVF_CHECK_ARG(out_cpad == 0 || out_cpad >= C, "freeze_fwd: out_cpad (%d) < C (%d)", out_cpad, C);
   hipStream_t s = (hipStream_t)stream;
   if (out_cpad == 4 && C <= 4) {
-    hipLaunchKernelGGL(freeze_fwd_cl4_kernel, dim3(grid_for((size_t)B * HW)), dim3(256), 0, s, x, mask,
+    hipLaunchKernelGGL(freeze_fwd_cl4_kernel, dim3(grid_for((size_t)B * HW, 256, 2048)), dim3(256), 0, s, x, mask,
                        p, B, C, T, HW, mask_per_clip);
   } else {
     if (out_cpad > C) {
       // pad channels must read as zero for the conv that consumes them
       size_t n = (size_t)B * T * HW * out_cpad;
-      hipLaunchKernelGGL(zero_kernel, dim3(grid_for(n)), dim3(256), 0, s, p, n);
+      hipLaunchKernelGGL(zero_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, s, p, n);
     }
-    hipLaunchKernelGGL(freeze_fwd_kernel, dim3(grid_for((size_t)B * C * HW)), dim3(256), 0, s, x, mask,
+    hipLaunchKernelGGL(freeze_fwd_kernel, dim3(grid_for((size_t)B * C * HW, 256, 2048)), dim3(256), 0, s, x, mask,
                        p, B, C, T, HW, mask_per_clip, out_cpad);
   }
   IVF_CHECK_LAUNCH();
@@ -580,9 +575,9 @@ extern "C" int ivf_reverse_fwd(const float* x, const int* partner, const float* 
   hipStream_t s = (hipStream_t)stream;
   if (out_cpad > C) {
     size_t n = (size_t)B * T * HW * out_cpad;
-    hipLaunchKernelGGL(zero_kernel, dim3(grid_for(n)), dim3(256), 0, s, p, n);
+    hipLaunchKernelGGL(zero_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, s, p, n);
   }
-  hipLaunchKernelGGL(reverse_fwd_kernel, dim3(grid_for((size_t)B * C * T * HW)), dim3(256), 0, s, x,
+  hipLaunchKernelGGL(reverse_fwd_kernel, dim3(grid_for((size_t)B * C * T * HW, 256, 2048)), dim3(256), 0, s, x,
                      partner, weight, p, B, C, T, HW, out_cpad);
   IVF_CHECK_LAUNCH();
   return IVF_OK;
@@ -733,7 +728,7 @@ extern "C" int ivf_clip_ingest_u8(const unsigned char* frames, float* out, int B
   IVF_CHECK_ARG(layout == IVF_INGEST_NCTHW || (layout == IVF_INGEST_CL && cpad >= C),
                 "clip_ingest: layout must be NCTHW or channels-last with cpad >= C");
   const size_t total = (size_t)B * T * (((size_t)H * W + 3) / 4);
-  hipLaunchKernelGGL(clip_ingest_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, frames, out, B, T,
+  hipLaunchKernelGGL(clip_ingest_kernel, dim3(grid_for(total, 256, 2048)), dim3(256), 0, (hipStream_t)stream, frames, out, B, T,
                      H * W, C, layout, cpad);
   IVF_CHECK_LAUNCH();
   return IVF_OK;
@@ -957,13 +952,13 @@ extern "C" int ivf_blob_stage(const float* x, int b, int C, int T, int HW, int m
                 "blob_stage: out_cpad must be 0 (NCTHW) or 4 (16-byte channels-last, C <= 4)");
   hipStream_t s = (hipStream_t)stream;
   if (out_cpad == 4) {
-    hipLaunchKernelGGL(blob_stage_cl4_kernel, dim3(grid_for((size_t)count * HW)), dim3(256), 0, s, x, p, C, T, HW,
+    hipLaunchKernelGGL(blob_stage_cl4_kernel, dim3(grid_for((size_t)count * HW, 256, 2048)), dim3(256), 0, s, x, p, C, T, HW,
                        n, first, count, mode);
   } else if (HW % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)p & 15) == 0) {
-    hipLaunchKernelGGL(blob_stage_ncthw_kernel<4>, dim3(grid_for((size_t)count * C * HW / 4)), dim3(256), 0, s, x, p,
+    hipLaunchKernelGGL(blob_stage_ncthw_kernel<4>, dim3(grid_for((size_t)count * C * HW / 4, 256, 2048)), dim3(256), 0, s, x, p,
                        C, T, HW, n, first, count, mode);
   } else {
-    hipLaunchKernelGGL(blob_stage_ncthw_kernel<1>, dim3(grid_for((size_t)count * C * HW)), dim3(256), 0, s, x, p, C,
+    hipLaunchKernelGGL(blob_stage_ncthw_kernel<1>, dim3(grid_for((size_t)count * C * HW, 256, 2048)), dim3(256), 0, s, x, p, C,
                        T, HW, n, first, count, mode);
   }
   IVF_CHECK_LAUNCH();

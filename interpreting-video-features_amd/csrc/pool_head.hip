@@ -1197,11 +1197,6 @@ __global__ __launch_bounds__(256) void cam_resize_norm_kernel(const float* __res
   }
 }
 
-static inline int grid_for(size_t total, int block = 256, int cap = 4096) {
-  size_t g = (total + block - 1) / block;
-  return (int)(g > (size_t)cap ? cap : (g ? g : 1));
-}
-
 static int check_pool(const ivf_pool3d_desc* d) {
   IVF_CHECK_ARG(d, "pool: null descriptor");
   IVF_CHECK_ARG(d->B > 0 && d->Ti > 0 && d->Hi > 0 && d->Wi > 0 && d->To > 0 && d->Ho > 0 && d->Wo > 0,
@@ -1355,15 +1350,20 @@ static int head_fwd_impl(const T* feat, const float* w, const float* bias, float
   return IVF_OK;
 }
 
+int ivf::head_fwd(const void* feat, bool bf16, const float* w, const float* bias, float* pooled, float* logits,
+                  float* probs, int B, int npos, int C, int K, int softmax, hipStream_t s) {
+  if (bf16) return head_fwd_impl<bf16s>((const bf16s*)feat, w, bias, pooled, logits, probs, B, npos, C, K, softmax, s);
+  return head_fwd_impl<float>((const float*)feat, w, bias, pooled, logits, probs, B, npos, C, K, softmax, s);
+}
 extern "C" int ivf_head_fwd(const float* feat, const float* w, const float* bias, float* pooled,
                             float* logits, float* probs, int B, int npos, int C, int K, int softmax,
                             ivf_stream_t stream) {
-  return head_fwd_impl<float>(feat, w, bias, pooled, logits, probs, B, npos, C, K, softmax, stream);
+  return head_fwd(feat, false, w, bias, pooled, logits, probs, B, npos, C, K, softmax, (hipStream_t)stream);
 }
 extern "C" int ivf_head_fwd_bf16(const void* feat, const float* w, const float* bias, float* pooled,
                                  float* logits, float* probs, int B, int npos, int C, int K, int softmax,
                                  ivf_stream_t stream) {
-  return head_fwd_impl<bf16s>((const bf16s*)feat, w, bias, pooled, logits, probs, B, npos, C, K, softmax, stream);
+  return head_fwd(feat, true, w, bias, pooled, logits, probs, B, npos, C, K, softmax, (hipStream_t)stream);
 }
 
 extern "C" int ivf_argmax(const float* probs, int b, int K, int* target, ivf_stream_t stream) {
@@ -1390,16 +1390,26 @@ static int head_bwd_impl(const T* feat, const float* w, const float* probs, cons
   return IVF_OK;
 }
 
+int ivf::head_bwd(const void* feat, bool bf16, const float* w, const float* probs, const int* target, const float* dout,
+                  float* score, float* dpooled, void* dfeat, int B, int npos, int C, int K, int softmax, int gate_relu,
+                  hipStream_t s) {
+  if (bf16)
+    return head_bwd_impl<bf16s>((const bf16s*)feat, w, probs, target, dout, score, dpooled, (bf16s*)dfeat, B, npos, C, K,
+                                softmax, gate_relu, s);
+  return head_bwd_impl<float>((const float*)feat, w, probs, target, dout, score, dpooled, (float*)dfeat, B, npos, C, K,
+                              softmax, gate_relu, s);
+}
 extern "C" int ivf_head_bwd(const float* feat, const float* w, const float* probs, const int* target,
                             const float* dout, float* score, float* dpooled, float* dfeat, int B,
                             int npos, int C, int K, int softmax, int gate_relu, ivf_stream_t stream) {
-  return head_bwd_impl<float>(feat, w, probs, target, dout, score, dpooled, dfeat, B, npos, C, K, softmax, gate_relu, stream);
+  return head_bwd(feat, false, w, probs, target, dout, score, dpooled, dfeat, B, npos, C, K, softmax, gate_relu,
+                  (hipStream_t)stream);
 }
 extern "C" int ivf_head_bwd_bf16(const void* feat, const float* w, const float* probs, const int* target,
                                  const float* dout, float* score, float* dpooled, void* dfeat, int B,
                                  int npos, int C, int K, int softmax, int gate_relu, ivf_stream_t stream) {
-  return head_bwd_impl<bf16s>((const bf16s*)feat, w, probs, target, dout, score, dpooled, (bf16s*)dfeat, B, npos, C, K,
-                              softmax, gate_relu, stream);
+  return head_bwd(feat, true, w, probs, target, dout, score, dpooled, dfeat, B, npos, C, K, softmax, gate_relu,
+                  (hipStream_t)stream);
 }
 
 template <class T>
@@ -1416,13 +1426,18 @@ static int gradcam_reduce_impl(const T* feat, const T* grad, float* weights, flo
   return IVF_OK;
 }
 
+int ivf::gradcam_reduce(const void* feat, const void* grad, bool bf16, float* weights, float* cam, int B, int npos,
+                        int C, hipStream_t s) {
+  if (bf16) return gradcam_reduce_impl<bf16s>((const bf16s*)feat, (const bf16s*)grad, weights, cam, B, npos, C, s);
+  return gradcam_reduce_impl<float>((const float*)feat, (const float*)grad, weights, cam, B, npos, C, s);
+}
 extern "C" int ivf_gradcam_reduce(const float* feat, const float* grad, float* weights, float* cam,
                                   int B, int npos, int C, ivf_stream_t stream) {
-  return gradcam_reduce_impl<float>(feat, grad, weights, cam, B, npos, C, stream);
+  return gradcam_reduce(feat, grad, false, weights, cam, B, npos, C, (hipStream_t)stream);
 }
 extern "C" int ivf_gradcam_reduce_bf16(const void* feat, const void* grad, float* weights, float* cam,
                                        int B, int npos, int C, ivf_stream_t stream) {
-  return gradcam_reduce_impl<bf16s>((const bf16s*)feat, (const bf16s*)grad, weights, cam, B, npos, C, stream);
+  return gradcam_reduce(feat, grad, true, weights, cam, B, npos, C, (hipStream_t)stream);
 }
 
 extern "C" int ivf_cam_resize_normalise(const float* cam, float* out, float* minmax_ws, int B, int nslice,

@@ -1,0 +1,116 @@
+// Host sequencing shared by the three backbones (I3D, CLSTM_4, the TF ConvLSTM2D classifier): the mask search loop,
+// the perturb-and-forward step and the chunk loop of the one-blob search.  Internal: not part of include/ivf_hip.h.
+// A backbone provides a Backbone view of its plan (below); the extern "C" entries check their arguments and call in.
+#pragma once
+#include <algorithm>
+
+#include "ivf_common.h"
+
+namespace ivf {
+
+// Per-plan scratch of the search loop: byte offsets into the plan's workspace.
+struct SearchScratch {
+  size_t score = 0, sig = 0, terms = 0, dreg = 0, dsig = 0, fbwd = 0;
+  size_t partner = 0, weight = 0;   // 'reverse' pairing rows, int [B,T] and float [B,T] (plans with a reverse mode)
+
+  // `take(bytes)` is the plan's workspace allocator; the order and the sizes are part of every plan's layout.
+  template <class Take>
+  void carve(Take&& take, size_t B, size_t T) {
+    score = take(B * 4);
+    sig = take(B * T * 4);
+    terms = take(B * 2 * 4);
+    dreg = take(B * T * 4);
+    dsig = take(B * T * 4);
+    fbwd = take(ivf_freeze_bwd_workspace_bytes((int)B, (int)T));
+  }
+  // The pairing kernels need B*T*8 bytes (partner + weight).  The ConvLSTM plan takes exactly that; the I3D plan has
+  // always taken B*T*12, which is kept so that its workspace size does not move; the TF plan has no reverse mode.
+  template <class Take>
+  void carve_pairs(Take&& take, size_t B, size_t T, size_t bytes_per_frame) {
+    partner = take(B * T * bytes_per_frame);
+    weight = partner + B * T * sizeof(int);
+  }
+};
+
+// What the shared code needs from a plan.  `forward` runs the network on the b rows staged in `in` (probs_out
+// optional; the plan's own `probs` buffer is always written); `backward` is backward-data of that forward for
+// target[b] into `din`, writing score[b].
+struct Backbone {
+  void* plan;
+  int B, C, T, HW, K;         // plan batch, clip geometry, classes
+  int layout;                 // of in / din, as the mask kernels name it: 0 NCTHW, 4 16-byte channels-last pixels
+  float *in, *din;            // staged input and its gradient
+  const float* probs;         // [B,K] of the last forward
+  char* ws;
+  const SearchScratch* sc;
+  int (*forward)(void* plan, int b, float* probs_out, hipStream_t s);
+  int (*backward)(void* plan, int b, const int* target, float* score, hipStream_t s);
+
+  template <class U>
+  U* at(size_t off) const { return (U*)(ws + off); }
+};
+
+// x perturbed by `mask` [b,T] (values in [0,1]) into the staged input: mode 0 freeze, 1 reverse (mask.py:38-57)
+static inline int stage_perturbed(const Backbone& v, const float* x, const float* mask, int b, int mode, hipStream_t s) {
+  if (mode == 0) return ivf_freeze_fwd(x, mask, v.in, b, v.C, v.T, v.HW, 1, v.layout, s);
+  int* partner = v.at<int>(v.sc->partner);
+  float* weight = v.at<float>(v.sc->weight);
+  IVF_PROPAGATE(ivf_submask_pairs_batched(mask, b, v.T, 0.1f, partner, weight, s));
+  return ivf_reverse_fwd_batched(x, partner, weight, v.in, b, v.C, v.T, v.HW, v.layout, s);
+}
+
+static inline int run_perturbed_forward(const Backbone& v, const float* x, const float* mask, int b, int mode,
+                                        float* probs, hipStream_t s) {
+  IVF_PROPAGATE(stage_perturbed(v, x, mask, b, mode, s));
+  return v.forward(v.plan, b, probs, s);
+}
+
+// N iterations of the hot loop (FindMasksComparison_I3D_smth.py:193-214): sigmoid + L1 + TV, perturb, network forward
+// and backward, perturbation backward, Adam.  eps_at(step) is the Adam epsilon of step `step` (torch: eps itself;
+// tf.train.Adam: see ivf_tfclstm_search).  prof_set_iteration only gates the launch profiler of the conv3d launchers,
+// which the I3D plan alone reaches, so it is called for every backbone.
+template <class EpsAt>
+static int run_search(const Backbone& v, const float* x, int b, const int* target, float* raw_mask, float* exp_avg,
+                      float* exp_avg_sq, float lam1, float lam2, float lr, float beta1, float beta2, EpsAt eps_at,
+                      int N, int first_step, int mode, float* traj, hipStream_t s) {
+  const SearchScratch& c = *v.sc;
+  float *sig = v.at<float>(c.sig), *terms = v.at<float>(c.terms), *dreg = v.at<float>(c.dreg);
+  float *dsig = v.at<float>(c.dsig), *score = v.at<float>(c.score);
+  for (int it = 0; it < N; ++it) {
+    prof_set_iteration(it);
+    IVF_PROPAGATE(ivf_mask_reg(raw_mask, b, v.T, lam1, lam2, sig, terms, dreg, s));            // smth:198-200
+    IVF_PROPAGATE(stage_perturbed(v, x, sig, b, mode, s));                                      // smth:202
+    IVF_PROPAGATE(v.forward(v.plan, b, nullptr, s));                                            // smth:202-205
+    IVF_PROPAGATE(v.backward(v.plan, b, target, score, s));                                     // smth:213
+    if (mode == 0)
+      IVF_PROPAGATE(ivf_freeze_bwd(x, sig, v.din, dsig, nullptr, b, v.C, v.T, v.HW, 1, v.layout, v.at<void>(c.fbwd), s));
+    else
+      IVF_PROPAGATE(ivf_reverse_bwd(x, v.at<int>(c.partner), v.din, dsig, b, v.C, v.T, v.HW, v.layout,
+                                    v.at<void>(c.fbwd), s));
+    const int step = first_step + it;
+    IVF_PROPAGATE(ivf_search_step(raw_mask, sig, dsig, dreg, terms, score, exp_avg, exp_avg_sq,
+                                  traj ? traj + (size_t)it * b * 4 : nullptr, b, v.T, step, lr, beta1, beta2,
+                                  eps_at(step), s));                                            // smth:207-214
+  }
+  prof_set_iteration(-1);   // sampling off outside the loop
+  return IVF_OK;
+}
+
+// Exhaustive one-blob search (maskType 'combi'): the b*n candidates of b clips run in chunks of the plan's B rows --
+// stage straight into the input buffer, forward, pick the target score -- all on one stream, no host sync, no
+// allocation.  Chunks cross clip boundaries, so one clip still fills the plan.
+static inline int run_blob_scores(const Backbone& v, const float* x, int b, const int* target, int max_len, int mode,
+                                  float* scores, hipStream_t s) {
+  const int n = ivf_blob_count(v.T, max_len);
+  if (n < 0) return IVF_ERR_BAD_ARG;
+  const long long total = (long long)b * n;
+  for (long long first = 0; first < total; first += v.B) {
+    const int cnt = (int)std::min<long long>(v.B, total - first);
+    IVF_PROPAGATE(ivf_blob_stage(x, b, v.C, v.T, v.HW, max_len, mode, first, cnt, v.in, v.layout, s));
+    IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
+    IVF_PROPAGATE(blob_pick(v.probs, target, v.K, n, first, cnt, scores, s));
+  }
+  return IVF_OK;
+}
+
+}  // namespace ivf

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "ivf_common.h"
+#include "search_driver.h"
 
 namespace ivf {
 
@@ -368,11 +369,6 @@ __global__ __launch_bounds__(256) void tf_cam_resize_kernel(const float* __restr
   }
 }
 
-static inline int tf_grid(long total, int cap = 16384) {
-  long gsz = (total + 255) / 256;
-  return (int)(gsz > cap ? cap : (gsz ? gsz : 1));
-}
-
 struct TfLayerPlan {
   TfGeom g;
   size_t wx_off, bx_off, wh_off;                                  // floats in the weights arena (Keras layouts as given)
@@ -390,8 +386,8 @@ struct ivf_tfclstm {
   std::vector<TfLayerPlan> L;
   int feat = 0, fc_in = 0, fc_steps = 0, fc_first = 0;
   size_t fcw_off = 0, fcb_off = 0, weights_floats = 0, ws_bytes = 0;
-  size_t off_p, off_dp, off_flat, off_dflat, off_logits, off_probs, off_score, off_sig, off_terms, off_dreg, off_dsig,
-      off_fbwd, off_cam, off_fmax;
+  size_t off_p, off_dp, off_flat, off_dflat, off_logits, off_probs, off_cam, off_fmax;
+  SearchScratch sc;      // no pairing rows: this plan has no reverse mode
   float* wa = nullptr;
   char* ws = nullptr;
   bool head_loaded = false;
@@ -469,12 +465,7 @@ extern "C" int ivf_tfclstm_create(const ivf_tfclstm_config* c, ivf_tfclstm_t** o
   const int K = c->num_classes;
   n->off_logits = takeb(B * K * 4);
   n->off_probs = takeb(B * K * 4);
-  n->off_score = takeb(B * 4);
-  n->off_sig = takeb(B * T * 4);
-  n->off_terms = takeb(B * 2 * 4);
-  n->off_dreg = takeb(B * T * 4);
-  n->off_dsig = takeb(B * T * 4);
-  n->off_fbwd = takeb(ivf_freeze_bwd_workspace_bytes((int)B, (int)T));
+  n->sc.carve(takeb, B, T);
   n->ws_bytes = bytes;
   *out = n;
   return IVF_OK;
@@ -561,21 +552,21 @@ static int tf_run_forward(ivf_tfclstm* n, const float* x, int b, float* logits, 
     long sB, sC, sT;
     tf_in_strides(n, i, &sB, &sC, &sT);
     const long plane = (long)g.Ho * g.Wo;
-    hipLaunchKernelGGL(tf_xconv_fwd_kernel, dim3(tf_grid((long)b * T * g.F * plane)), dim3(256), 0, s, in, n->wa + p.wx_off,
+    hipLaunchKernelGGL(tf_xconv_fwd_kernel, dim3(grid_for((long)b * T * g.F * plane, 256, 16384)), dim3(256), 0, s, in, n->wa + p.wx_off,
                        n->wa + p.bx_off, n->wsf(p.zx_off), b, T, sB, sC, sT, g);
     IVF_CHECK_LAUNCH();
     for (int t = 0; t < T; ++t) {
-      hipLaunchKernelGGL(tf_step_fwd_kernel, dim3(tf_grid((long)b * g.F * plane)), dim3(256), 0, s, n->wsf(p.zx_off),
+      hipLaunchKernelGGL(tf_step_fwd_kernel, dim3(grid_for((long)b * g.F * plane, 256, 16384)), dim3(256), 0, s, n->wsf(p.zx_off),
                          n->wa + p.wh_off, n->wsf(p.S_off), n->wsf(p.H_off), b, T, t, c.recurrent_hard_sigmoid, g);
       IVF_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(tf_pool_fwd_kernel, dim3(tf_grid((long)b * T * g.F * g.Hp * g.Wp)), dim3(256), 0, s, n->wsf(p.H_off),
+    hipLaunchKernelGGL(tf_pool_fwd_kernel, dim3(grid_for((long)b * T * g.F * g.Hp * g.Wp, 256, 16384)), dim3(256), 0, s, n->wsf(p.H_off),
                        n->wsf(p.X_off), n->at<unsigned char>(p.arg_off), (long)b * T * g.F, g.Ho, g.Wo, g.Hp, g.Wp);
     IVF_CHECK_LAUNCH();
   }
   const TfGeom& top = n->L.back().g;
   float* flat = n->at<float>(n->off_flat);
-  hipLaunchKernelGGL(tf_flatten_kernel, dim3(tf_grid((long)b * n->fc_in)), dim3(256), 0, s, n->wsf(n->L.back().X_off), flat, b,
+  hipLaunchKernelGGL(tf_flatten_kernel, dim3(grid_for((long)b * n->fc_in, 256, 16384)), dim3(256), 0, s, n->wsf(n->L.back().X_off), flat, b,
                      T, top.F, top.Hp, top.Wp, n->fc_first, n->fc_steps, 1);
   IVF_CHECK_LAUNCH();
   float* lg = n->at<float>(n->off_logits);
@@ -599,10 +590,10 @@ static int tf_head_backward(ivf_tfclstm* n, int b, const int* target, float* sco
                      n->at<float>(n->off_probs), target, score, dflat, n->fc_in, c.num_classes, wrt_logit);
   IVF_CHECK_LAUNCH();
   IVF_CHECK_HIP(hipMemsetAsync(n->wsf(top.dX_off), 0, (size_t)b * c.T * g.F * g.Hp * g.Wp * 4, s));
-  hipLaunchKernelGGL(tf_flatten_kernel, dim3(tf_grid((long)b * n->fc_in)), dim3(256), 0, s, n->wsf(top.dX_off), dflat, b, c.T,
+  hipLaunchKernelGGL(tf_flatten_kernel, dim3(grid_for((long)b * n->fc_in, 256, 16384)), dim3(256), 0, s, n->wsf(top.dX_off), dflat, b, c.T,
                      g.F, g.Hp, g.Wp, n->fc_first, n->fc_steps, 0);
   IVF_CHECK_LAUNCH();
-  hipLaunchKernelGGL(tf_unpool_bwd_kernel, dim3(tf_grid((long)b * c.T * g.F * g.Ho * g.Wo)), dim3(256), 0, s, n->wsf(top.dX_off),
+  hipLaunchKernelGGL(tf_unpool_bwd_kernel, dim3(grid_for((long)b * c.T * g.F * g.Ho * g.Wo, 256, 16384)), dim3(256), 0, s, n->wsf(top.dX_off),
                      n->at<unsigned char>(top.arg_off), n->wsf(top.dHd_off), (long)b * c.T * g.F, g.Ho, g.Wo, g.Hp, g.Wp);
   IVF_CHECK_LAUNCH();
   return IVF_OK;
@@ -617,12 +608,12 @@ static int tf_run_backward(ivf_tfclstm* n, int b, const int* target, float* scor
     const TfGeom& g = p.g;
     const long plane = (long)g.Ho * g.Wo;
     if (i != (int)n->L.size() - 1) {
-      hipLaunchKernelGGL(tf_unpool_bwd_kernel, dim3(tf_grid((long)b * T * g.F * plane)), dim3(256), 0, s, n->wsf(p.dX_off),
+      hipLaunchKernelGGL(tf_unpool_bwd_kernel, dim3(grid_for((long)b * T * g.F * plane, 256, 16384)), dim3(256), 0, s, n->wsf(p.dX_off),
                          n->at<unsigned char>(p.arg_off), n->wsf(p.dHd_off), (long)b * T * g.F, g.Ho, g.Wo, g.Hp, g.Wp);
       IVF_CHECK_LAUNCH();
     }
     for (int t = T - 1; t >= 0; --t) {
-      hipLaunchKernelGGL(tf_step_bwd_kernel, dim3(tf_grid((long)b * g.F * plane)), dim3(256), 0, s, n->wsf(p.dHd_off),
+      hipLaunchKernelGGL(tf_step_bwd_kernel, dim3(grid_for((long)b * g.F * plane, 256, 16384)), dim3(256), 0, s, n->wsf(p.dHd_off),
                          n->wa + p.wh_off, n->wsf(p.S_off), n->wsf(p.dZ_off), n->wsf(p.dC_off), b, T, t,
                          c.recurrent_hard_sigmoid, g);
       IVF_CHECK_LAUNCH();
@@ -630,11 +621,34 @@ static int tf_run_backward(ivf_tfclstm* n, int b, const int* target, float* scor
     float* out = i == 0 ? dx : n->wsf(n->L[i - 1].dX_off);
     long sB, sC, sT;
     tf_in_strides(n, i, &sB, &sC, &sT);
-    hipLaunchKernelGGL(tf_xconv_bwd_kernel, dim3(tf_grid((long)b * T * g.Cin * g.Hin * g.Win)), dim3(256), 0, s, n->wsf(p.dZ_off),
+    hipLaunchKernelGGL(tf_xconv_bwd_kernel, dim3(grid_for((long)b * T * g.Cin * g.Hin * g.Win, 256, 16384)), dim3(256), 0, s, n->wsf(p.dZ_off),
                        n->wa + p.wx_off, out, b, T, sB, sC, sT, g);
     IVF_CHECK_LAUNCH();
   }
   return IVF_OK;
+}
+
+// the plan as the shared search driver sees it: the clip is staged NCTHW in P, its gradient lands in dP
+static Backbone backbone(ivf_tfclstm* n) {
+  const ivf_tfclstm_config& c = n->cfg;
+  Backbone v{};
+  v.plan = n;
+  v.B = c.B; v.C = c.C; v.T = c.T; v.HW = c.H * c.W; v.K = c.num_classes;
+  v.layout = 0;
+  v.in = n->at<float>(n->off_p);
+  v.din = n->at<float>(n->off_dp);
+  v.probs = n->at<float>(n->off_probs);
+  v.ws = n->ws;
+  v.sc = &n->sc;
+  v.forward = [](void* p, int b, float* probs, hipStream_t s) {
+    ivf_tfclstm* n = (ivf_tfclstm*)p;
+    return tf_run_forward(n, n->at<float>(n->off_p), b, nullptr, probs, s);
+  };
+  v.backward = [](void* p, int b, const int* target, float* score, hipStream_t s) {
+    ivf_tfclstm* n = (ivf_tfclstm*)p;
+    return tf_run_backward(n, b, target, score, n->at<float>(n->off_dp), s);
+  };
+  return v;
 }
 
 }  // namespace ivf
@@ -655,11 +669,8 @@ extern "C" int ivf_tfclstm_perturbed_forward(ivf_tfclstm_t* n, const float* x, i
                                              ivf_stream_t stream) {
   IVF_PROPAGATE(tf_ready(n, b));
   IVF_CHECK_ARG(x && mask, "tfclstm_perturbed_forward: bad args");
-  const ivf_tfclstm_config& c = n->cfg;
-  hipStream_t s = (hipStream_t)stream;
-  float* P = n->at<float>(n->off_p);
-  IVF_PROPAGATE(ivf_freeze_fwd(x, mask, P, b, c.C, c.T, c.H * c.W, 1, 0, s));       // the tf.scan recurrence, find_mask_kth.py:318-327
-  return tf_run_forward(n, P, b, nullptr, probs, s);
+  // freeze only: the tf.scan recurrence, find_mask_kth.py:318-327
+  return run_perturbed_forward(backbone(n), x, mask, b, 0, probs, (hipStream_t)stream);
 }
 
 // the loop of find_mask_kth.py:356-372,431-452: sigmoid, L1 + TV, tf.scan freeze, model, softmax score, tf.train.Adam
@@ -669,28 +680,9 @@ extern "C" int ivf_tfclstm_search(ivf_tfclstm_t* n, const float* x, int b, const
                                   int N, int first_step, float* traj, ivf_stream_t stream) {
   IVF_PROPAGATE(tf_ready(n, b));
   IVF_CHECK_ARG(x && target && raw_mask && exp_avg && exp_avg_sq && N >= 0 && first_step >= 1, "tfclstm_search: bad args");
-  const ivf_tfclstm_config& c = n->cfg;
-  hipStream_t s = (hipStream_t)stream;
-  const int T = c.T, HW = c.H * c.W;
-  float* sig = n->at<float>(n->off_sig);
-  float* terms = n->at<float>(n->off_terms);
-  float* dreg = n->at<float>(n->off_dreg);
-  float* dsig = n->at<float>(n->off_dsig);
-  float* score = n->at<float>(n->off_score);
-  float* P = n->at<float>(n->off_p);
-  float* dP = n->at<float>(n->off_dp);
-  for (int it = 0; it < N; ++it) {
-    IVF_PROPAGATE(ivf_mask_reg(raw_mask, b, T, lam1, lam2, sig, terms, dreg, s));
-    IVF_PROPAGATE(ivf_freeze_fwd(x, sig, P, b, c.C, T, HW, 1, 0, s));
-    IVF_PROPAGATE(tf_run_forward(n, P, b, nullptr, nullptr, s));
-    IVF_PROPAGATE(tf_run_backward(n, b, target, score, dP, s));
-    IVF_PROPAGATE(ivf_freeze_bwd(x, sig, dP, dsig, nullptr, b, c.C, T, HW, 1, 0, n->at<void>(n->off_fbwd), s));
-    const int step = first_step + it;
-    const float eps_hat = eps / sqrtf(1.f - powf(beta2, (float)step));
-    IVF_PROPAGATE(ivf_search_step(raw_mask, sig, dsig, dreg, terms, score, exp_avg, exp_avg_sq,
-                                  traj ? traj + (size_t)it * b * 4 : nullptr, b, T, step, lr, beta1, beta2, eps_hat, s));
-  }
-  return IVF_OK;
+  auto eps_hat = [=](int step) { return eps / sqrtf(1.f - powf(beta2, (float)step)); };
+  return run_search(backbone(n), x, b, target, raw_mask, exp_avg, exp_avg_sq, lam1, lam2, lr, beta1, beta2, eps_hat, N,
+                    first_step, 0, traj, (hipStream_t)stream);
 }
 
 // gradcam.py:28-99 for b clips: forward of the UNPERTURBED clip as the graph sees it with mask_var = 0 (the caller passes

@@ -31,25 +31,6 @@ def _mode_id(mode):
     raise UnboundLocalError("local variable 'perturbed_input' referenced before assignment")
 
 
-def _blob_scores(eng, fn, x, target, max_len, mode):
-    """Shared body of I3DEngine.blob_scores / CLSTMEngine.blob_scores: the whole one-blob grid of b clips in one C
-    call (chunks of the plan's max_batch rows; b itself may exceed max_batch)."""
-    L.require_gpu(x)
-    x = L.f32c(x)
-    if x.dim() != 5 or tuple(x.shape[1:]) != eng.clip_shape:
-        raise L.IvfError(f"clip batch must be [b,{','.join(map(str, eng.clip_shape))}], got {tuple(x.shape)}")
-    b, T = x.shape[0], eng.clip_shape[1]
-    ml = T if max_len is None else int(max_len)
-    n = L.lib().ivf_blob_count(T, ml)
-    if n < 0:
-        raise L.IvfError(L.lib().ivf_last_error().decode())
-    tgt = eng._targets(target, b)
-    scores = torch.empty(b, n, device=eng.device)
-    with torch.cuda.device(eng.device):
-        L.check(fn(eng._h, L.ptr(x), b, L.ptr(tgt), ml, _mode_id(mode), L.ptr(scores), L.stream()))
-    return scores
-
-
 def _arena(nbytes, device):
     # torch's caching allocator returns >=512-byte aligned blocks
     t = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
@@ -57,19 +38,164 @@ def _arena(nbytes, device):
     return t
 
 
-class I3DEngine:
-    """Plan + arenas for `models.I3D_doubled{,_kth}.Model` on `max_batch` clips of
-    geometry [C,T,H,W] (reference Model.forward, I3D_doubled.py:351-380)."""
+class _Engine:
+    """What the three backbones share: one libivf_hip plan `ivf_<_prefix>_*`, its two arenas and the entry points every
+    plan has.  A subclass fills its config struct, calls `_create`, and loads its weights."""
+    _prefix = None
+    _has_mode = True        # the plan's search / perturbed_forward take the perturbation type (not the TF plan)
 
-    def __init__(self, num_classes, clip_shape, max_batch=1, stride_mod_layers="", last_stride=1,
-                 head_hw=(7, 7), head_time_base=2, softmax=True, device=None, math=None):
+    def __init__(self, num_classes, clip_shape, max_batch, device):
         L.require_gpu()
         self.device = torch.device(device if device is not None else "cuda")
         C, T, H, W = clip_shape
+        self.clip_shape = (C, T, H, W)
+        self.max_batch = int(max_batch)
+        self.K = int(num_classes)
+
+    def _fn(self, name):
+        return getattr(L.lib(), f"ivf_{self._prefix}_{name}")
+
+    def _create(self, cfg):
+        """cfg: the plan's config struct, geometry and class count filled in here; create -> arenas -> bind."""
+        cfg.B, cfg.num_classes = self.max_batch, self.K
+        cfg.C, cfg.T, cfg.H, cfg.W = self.clip_shape
+        self.cfg = cfg
+        self._h = c_void_p()
+        L.check(self._fn("create")(byref(cfg), byref(self._h)))
+        with torch.cuda.device(self.device):
+            self._weights = _arena(self._fn("weights_bytes")(self._h), self.device)
+            self._ws = _arena(self._fn("workspace_bytes")(self._h), self.device)
+        L.check(self._fn("bind")(self._h, L.ptr(self._weights), L.ptr(self._ws)))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and L is not None and getattr(L, "_lib", None) is not None:
+            getattr(L._lib, f"ivf_{self._prefix}_destroy")(h)
+            self._h = c_void_p()
+
+    @property
+    def workspace_bytes(self):
+        return self._ws.numel()
+
+    # -------------------------------------------------------------- helpers
+    def _param(self, sd, key):
+        """state_dict tensor `key` (reference key scheme, optional 'module.' prefix, numpy accepted) on the device."""
+        for k in (key, "module." + key):
+            if k in sd:
+                v = sd[k]
+                if isinstance(v, np.ndarray):
+                    v = torch.from_numpy(v)
+                return L.f32c(v.detach().to(self.device))
+        raise KeyError(f"state_dict is missing '{key}'")
+
+    def _clip(self, x, any_batch=False):
+        L.require_gpu(x)
+        x = L.f32c(x)
+        if x.dim() != 5 or tuple(x.shape[1:]) != self.clip_shape:
+            raise L.IvfError(f"clip batch must be [b,{','.join(map(str, self.clip_shape))}], got {tuple(x.shape)}")
+        if x.shape[0] > self.max_batch and not any_batch:
+            raise L.IvfError(f"batch {x.shape[0]} exceeds the plan's maximum {self.max_batch}")
+        return x
+
+    def _targets(self, target, b):
+        t = torch.as_tensor(target, device=self.device).to(torch.int32).reshape(-1).contiguous()
+        if t.numel() != b:
+            raise L.IvfError(f"need {b} targets, got {t.numel()}")
+        return t
+
+    def _mode_args(self, mode):
+        return (_mode_id(mode),) if self._has_mode else ()
+
+    # -------------------------------------------------------------- entry points
+    def forward(self, x, want_logits=False):
+        x = self._clip(x)
+        b = x.shape[0]
+        probs = torch.empty(b, self.K, device=self.device)
+        logits = torch.empty(b, self.K, device=self.device) if want_logits else None
+        with torch.cuda.device(self.device):
+            L.check(self._fn("forward")(self._h, L.ptr(x), b, L.ptr(logits), L.ptr(probs), L.stream()))
+        return (probs, logits) if want_logits else probs
+
+    def backward(self, b, target=None, dout=None, want_dx=True):
+        """Backward-data of the last forward.  Returns (score [b] or None, dx NCTHW or None)."""
+        C, T, H, W = self.clip_shape
+        tgt = self._targets(target, b) if target is not None else None
+        dout = L.f32c(dout) if dout is not None else None
+        score = torch.empty(b, device=self.device) if tgt is not None else None
+        dx = torch.empty(b, C, T, H, W, device=self.device) if want_dx else None
+        with torch.cuda.device(self.device):
+            L.check(self._fn("backward")(self._h, b, L.ptr(tgt), L.ptr(dout), L.ptr(score), L.ptr(dx), L.stream()))
+        return score, dx
+
+    def search(self, x, target, raw_mask, lam1, lam2, N, lr=0.2, betas=(0.9, 0.999), eps=1e-8,
+               state=None, want_traj=True, mode="freeze"):
+        """N iterations of the hot loop (smth:193-214) on b clips.  raw_mask [b,T] is
+        updated in place; state = (exp_avg, exp_avg_sq, steps_done) continues a search;
+        mode = the perturbation the loop optimises through (temporalMaskType, smth:121,202)."""
+        x = self._clip(x)
+        b = x.shape[0]
+        T = self.clip_shape[1]
+        tgt = self._targets(target, b)
+        L.require_gpu(raw_mask)
+        if raw_mask.dtype != torch.float32 or not raw_mask.is_contiguous() or tuple(raw_mask.shape) != (b, T):
+            raise L.IvfError("raw_mask must be a contiguous float32 [b,T] tensor")
+        if state is None:
+            state = (torch.zeros_like(raw_mask), torch.zeros_like(raw_mask), 0)
+        m, v, done = state
+        traj = torch.empty(N, b, 4, device=self.device) if want_traj else None
+        with torch.cuda.device(self.device):
+            L.check(self._fn("search")(self._h, L.ptr(x), b, L.ptr(tgt), L.ptr(raw_mask), L.ptr(m), L.ptr(v),
+                                       lam1, lam2, lr, betas[0], betas[1], eps, int(N), done + 1,
+                                       *self._mode_args(mode), L.ptr(traj), L.stream()))
+        return traj, (m, v, done + int(N))
+
+    def perturbed_forward(self, x, mask, mode="freeze"):
+        x = self._clip(x)
+        b = x.shape[0]
+        mask = L.f32c(mask.to(self.device))
+        if tuple(mask.shape) != (b, self.clip_shape[1]):
+            raise L.IvfError("mask must be [b,T]")
+        probs = torch.empty(b, self.K, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(self._fn("perturbed_forward")(self._h, L.ptr(x), b, L.ptr(mask), *self._mode_args(mode),
+                                                  L.ptr(probs), L.stream()))
+        return probs
+
+    def blob_scores(self, x, target, max_len=None, mode="freeze"):
+        """Exhaustive one-blob search grid (maskType 'combi', ivf_*_blob_scores): scores [b, n] of target[clip]
+        under every one-blob binary mask, in the order of ivf_search.blob_candidates(T, max_len).  The whole grid of
+        b clips in one C call (chunks of the plan's max_batch rows; b itself may exceed max_batch)."""
+        x = self._clip(x, any_batch=True)
+        b, T = x.shape[0], self.clip_shape[1]
+        ml = T if max_len is None else int(max_len)
+        n = L.lib().ivf_blob_count(T, ml)
+        if n < 0:
+            raise L.IvfError(L.lib().ivf_last_error().decode())
+        tgt = self._targets(target, b)
+        scores = torch.empty(b, n, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(self._fn("blob_scores")(self._h, L.ptr(x), b, L.ptr(tgt), ml, _mode_id(mode), L.ptr(scores),
+                                            L.stream()))
+        return scores
+
+    def argmax(self, probs):
+        b = probs.shape[0]
+        t = torch.empty(b, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().ivf_argmax(L.ptr(L.f32c(probs)), b, probs.shape[1], L.ptr(t), L.stream()))
+        return t
+
+
+class I3DEngine(_Engine):
+    """Plan + arenas for `models.I3D_doubled{,_kth}.Model` on `max_batch` clips of
+    geometry [C,T,H,W] (reference Model.forward, I3D_doubled.py:351-380)."""
+    _prefix = "i3d"
+
+    def __init__(self, num_classes, clip_shape, max_batch=1, stride_mod_layers="", last_stride=1,
+                 head_hw=(7, 7), head_time_base=2, softmax=True, device=None, math=None):
+        super().__init__(num_classes, clip_shape, max_batch, device)
         sml = arch.parse_stride_mod(stride_mod_layers)
         cfg = L.I3DConfig()
-        cfg.B, cfg.C, cfg.T, cfg.H, cfg.W = int(max_batch), C, T, H, W
-        cfg.num_classes = int(num_classes)
         cfg.stem_stride_t = arch.temporal_stride('Conv3d_1a_7x7', sml, last_stride)
         cfg.pool4a_stride_t = arch.temporal_stride('MaxPool3d_4a_3x3', sml, last_stride)
         cfg.pool5a_stride_t = arch.temporal_stride('MaxPool3d_5a_2x2', sml, last_stride)
@@ -78,16 +204,7 @@ class I3DEngine:
         cfg.softmax = 1 if softmax else 0
         self.math = math if math is not None else DEFAULT_MATH
         cfg.math = L.MATH_MODES[self.math]
-        self.cfg = cfg
-        self.clip_shape = (C, T, H, W)
-        self.max_batch = int(max_batch)
-        self.K = int(num_classes)
-        self._h = c_void_p()
-        L.check(L.lib().ivf_i3d_create(byref(cfg), byref(self._h)))
-        with torch.cuda.device(self.device):
-            self._weights = _arena(L.lib().ivf_i3d_weights_bytes(self._h), self.device)
-            self._ws = _arena(L.lib().ivf_i3d_workspace_bytes(self._h), self.device)
-        L.check(L.lib().ivf_i3d_bind(self._h, L.ptr(self._weights), L.ptr(self._ws)))
+        self._create(cfg)
         self._tuned = False
         self.unit_names = []
         for i in range(L.lib().ivf_i3d_num_convs(self._h)):
@@ -95,27 +212,11 @@ class I3DEngine:
             L.check(L.lib().ivf_i3d_conv_info(self._h, i, name, None, None, None, None, None, None))
             self.unit_names.append(name.value.decode())
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value and L is not None and getattr(L, "_lib", None) is not None:
-            L._lib.ivf_i3d_destroy(h)
-            self._h = c_void_p()
-
-    @property
-    def workspace_bytes(self):
-        return self._ws.numel()
-
     # -------------------------------------------------------------- weights
     def load_state_dict(self, sd, bn_eps=1e-3, autotune=None):
         """sd: reference key scheme, optional 'module.' prefix."""
         def get(key):
-            for k in (key, "module." + key):
-                if k in sd:
-                    v = sd[k]
-                    if isinstance(v, np.ndarray):
-                        v = torch.from_numpy(v)
-                    return L.f32c(v.detach().to(self.device))
-            raise KeyError(f"state_dict is missing '{key}'")
+            return self._param(sd, key)
         keep = []
         with torch.cuda.device(self.device):
             for i, name in enumerate(self.unit_names):
@@ -175,44 +276,7 @@ class I3DEngine:
         L.check(L.lib().ivf_i3d_set_tuning(self._h, arr))
         self._tuned = True
 
-    # -------------------------------------------------------------- helpers
-    def _clip(self, x):
-        L.require_gpu(x)
-        x = L.f32c(x)
-        if x.dim() != 5 or tuple(x.shape[1:]) != self.clip_shape:
-            raise L.IvfError(f"clip batch must be [b,{','.join(map(str, self.clip_shape))}], got {tuple(x.shape)}")
-        if x.shape[0] > self.max_batch:
-            raise L.IvfError(f"batch {x.shape[0]} exceeds the plan's maximum {self.max_batch}")
-        return x
-
-    def _targets(self, target, b):
-        t = torch.as_tensor(target, device=self.device).to(torch.int32).reshape(-1).contiguous()
-        if t.numel() != b:
-            raise L.IvfError(f"need {b} targets, got {t.numel()}")
-        return t
-
-    # -------------------------------------------------------------- entry points
-    def forward(self, x, want_logits=False):
-        x = self._clip(x)
-        b = x.shape[0]
-        probs = torch.empty(b, self.K, device=self.device)
-        logits = torch.empty(b, self.K, device=self.device) if want_logits else None
-        with torch.cuda.device(self.device):
-            L.check(L.lib().ivf_i3d_forward(self._h, L.ptr(x), b, L.ptr(logits), L.ptr(probs), L.stream()))
-        return (probs, logits) if want_logits else probs
-
-    def backward(self, b, target=None, dout=None, want_dx=True):
-        """Backward-data of the last forward.  Returns (score [b] or None, dx NCTHW or None)."""
-        C, T, H, W = self.clip_shape
-        tgt = self._targets(target, b) if target is not None else None
-        dout = L.f32c(dout) if dout is not None else None
-        score = torch.empty(b, device=self.device) if tgt is not None else None
-        dx = torch.empty(b, C, T, H, W, device=self.device) if want_dx else None
-        with torch.cuda.device(self.device):
-            L.check(L.lib().ivf_i3d_backward(self._h, b, L.ptr(tgt), L.ptr(dout), L.ptr(score), L.ptr(dx),
-                                             L.stream()))
-        return score, dx
-
+    # -------------------------------------------------------------- entry points of this backbone alone
     def endpoint(self, name, b):
         """Activation of the last forward as an NCTHW torch tensor (copy)."""
         p = c_void_p()
@@ -224,52 +288,6 @@ class I3DEngine:
         esz = L.lib().ivf_i3d_act_elem_bytes(self._h)           # 2: bf16 storage (math="bf16act")
         flat = self._ws[off:off + esz * n].view(torch.float32 if esz == 4 else torch.bfloat16).float()
         return flat.view(b, T.value, H.value, W.value, ld.value)[..., :C.value].permute(0, 4, 1, 2, 3).contiguous()
-
-    def search(self, x, target, raw_mask, lam1, lam2, N, lr=0.2, betas=(0.9, 0.999), eps=1e-8,
-               state=None, want_traj=True, mode="freeze"):
-        """N iterations of the hot loop (smth:193-214) on b clips.  raw_mask [b,T] is
-        updated in place; state = (exp_avg, exp_avg_sq, steps_done) continues a search;
-        mode = the perturbation the loop optimises through (temporalMaskType, smth:121,202)."""
-        x = self._clip(x)
-        b = x.shape[0]
-        T = self.clip_shape[1]
-        tgt = self._targets(target, b)
-        L.require_gpu(raw_mask)
-        if raw_mask.dtype != torch.float32 or not raw_mask.is_contiguous() or tuple(raw_mask.shape) != (b, T):
-            raise L.IvfError("raw_mask must be a contiguous float32 [b,T] tensor")
-        if state is None:
-            state = (torch.zeros_like(raw_mask), torch.zeros_like(raw_mask), 0)
-        m, v, done = state
-        traj = torch.empty(N, b, 4, device=self.device) if want_traj else None
-        with torch.cuda.device(self.device):
-            L.check(L.lib().ivf_i3d_search(self._h, L.ptr(x), b, L.ptr(tgt), L.ptr(raw_mask), L.ptr(m), L.ptr(v),
-                                           lam1, lam2, lr, betas[0], betas[1], eps, int(N), done + 1,
-                                           _mode_id(mode), L.ptr(traj), L.stream()))
-        return traj, (m, v, done + int(N))
-
-    def perturbed_forward(self, x, mask, mode="freeze"):
-        x = self._clip(x)
-        b = x.shape[0]
-        mask = L.f32c(mask.to(self.device))
-        if tuple(mask.shape) != (b, self.clip_shape[1]):
-            raise L.IvfError("mask must be [b,T]")
-        probs = torch.empty(b, self.K, device=self.device)
-        with torch.cuda.device(self.device):
-            L.check(L.lib().ivf_i3d_perturbed_forward(self._h, L.ptr(x), b, L.ptr(mask),
-                                                      _mode_id(mode), L.ptr(probs), L.stream()))
-        return probs
-
-    def blob_scores(self, x, target, max_len=None, mode="freeze"):
-        """Exhaustive one-blob search grid (maskType 'combi', ivf_i3d_blob_scores): scores [b, n] of target[clip]
-        under every one-blob binary mask, in the order of ivf_search.blob_candidates(T, max_len)."""
-        return _blob_scores(self, L.lib().ivf_i3d_blob_scores, x, target, max_len, mode)
-
-    def argmax(self, probs):
-        b = probs.shape[0]
-        t = torch.empty(b, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            L.check(L.lib().ivf_argmax(L.ptr(L.f32c(probs)), b, probs.shape[1], L.ptr(t), L.stream()))
-        return t
 
     def gradcam(self, x, target=None, per_frame=True, out_hw=None, layer="Mixed_5c"):
         """GradCamVideo for b clips: (cam [b,T,H,W], probs [b,K]).  `layer`: the target endpoint
@@ -295,21 +313,19 @@ class I3DEngine:
         return cam, probs
 
 
-class CLSTMEngine:
+class CLSTMEngine(_Engine):
     """Plan + arenas for `models.CLSTM_4.Model` (reference CLSTM_4.py:69-85 over
     convolution_lstm.py:96-132) on `max_batch` clips [C,T,H,W]."""
+    _prefix = "clstm"
 
     def __init__(self, num_classes, clip_shape, max_batch=1, hidden=4, layers=2, kernel=5, stride=2,
                  softmax=False, batch_norm=True, out_step=None, out_steps=None, device=None, effective_steps=None):
         """effective_steps: the effective steps inside the clip (convolution_lstm.py:129-130), whose top-layer
         outputs are the map stack of Grad-CAM target 'clstm'; default: the steps that feed endFC."""
-        L.require_gpu()
-        self.device = torch.device(device if device is not None else "cuda")
-        C, T, H, W = clip_shape
+        super().__init__(num_classes, clip_shape, max_batch, device)
+        T = clip_shape[1]
         cfg = L.CLSTMConfig()
-        cfg.B, cfg.C, cfg.T, cfg.H, cfg.W = int(max_batch), C, T, H, W
         cfg.hidden, cfg.layers, cfg.kernel, cfg.stride = int(hidden), int(layers), int(kernel), int(stride)
-        cfg.num_classes = int(num_classes)
         cfg.softmax = 1 if softmax else 0
         cfg.batch_norm = 1 if batch_norm else 0
         cfg.out_step = T - 1 if out_step is None else int(out_step)
@@ -320,38 +336,17 @@ class CLSTMEngine:
             for i, sv in enumerate(out_steps):
                 cfg.out_steps[i] = int(sv)
             cfg.out_step = int(out_steps[-1])
-        self.cfg = cfg
-        self.clip_shape = (C, T, H, W)
-        self.max_batch = int(max_batch)
-        self.K = int(num_classes)
         self.layers = int(layers)
-        self._h = c_void_p()
-        L.check(L.lib().ivf_clstm_create(byref(cfg), byref(self._h)))
-        with torch.cuda.device(self.device):
-            self._weights = _arena(L.lib().ivf_clstm_weights_bytes(self._h), self.device)
-            self._ws = _arena(L.lib().ivf_clstm_workspace_bytes(self._h), self.device)
-        L.check(L.lib().ivf_clstm_bind(self._h, L.ptr(self._weights), L.ptr(self._ws)))
+        self._create(cfg)
         if effective_steps is None:
             effective_steps = list(out_steps) if out_steps is not None else [cfg.out_step]
         self.effective_steps = tuple(int(v) for v in effective_steps)
         L.check(L.lib().ivf_clstm_set_cam_steps(self._h, (c_int * len(self.effective_steps))(*self.effective_steps),
                                                 len(self.effective_steps)))
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value and L is not None and getattr(L, "_lib", None) is not None:
-            L._lib.ivf_clstm_destroy(h)
-            self._h = c_void_p()
-
     def load_state_dict(self, sd, bn_eps=1e-5):
         def get(key):
-            for k in (key, "module." + key):
-                if k in sd:
-                    v = sd[k]
-                    if isinstance(v, np.ndarray):
-                        v = torch.from_numpy(v)
-                    return L.f32c(v.detach().to(self.device))
-            raise KeyError(f"state_dict is missing '{key}'")
+            return self._param(sd, key)
         with torch.cuda.device(self.device):
             for i in range(self.layers):
                 ts = ([get(f"clstm.cell{i}.Wx{g}.weight") for g in "ifco"]
@@ -366,64 +361,8 @@ class CLSTMEngine:
                                                 L.stream()))
             torch.cuda.current_stream().synchronize()
 
-    _clip = I3DEngine._clip
-    _targets = I3DEngine._targets
-    argmax = I3DEngine.argmax
-
-    def forward(self, x, want_logits=False):
-        x = self._clip(x)
-        b = x.shape[0]
-        probs = torch.empty(b, self.K, device=self.device)
-        logits = torch.empty(b, self.K, device=self.device) if want_logits else None
-        with torch.cuda.device(self.device):
-            L.check(L.lib().ivf_clstm_forward(self._h, L.ptr(x), b, L.ptr(logits), L.ptr(probs), L.stream()))
-        return (probs, logits) if want_logits else probs
-
     def backward(self, b, target=None, dout=None, want_dx=True):
-        C, T, H, W = self.clip_shape
-        tgt = self._targets(target, b) if target is not None else None
-        dout = L.f32c(dout) if dout is not None else None
-        score = torch.empty(b, device=self.device) if tgt is not None else None
-        dx = torch.empty(b, C, T, H, W, device=self.device)
-        with torch.cuda.device(self.device):
-            L.check(L.lib().ivf_clstm_backward(self._h, b, L.ptr(tgt), L.ptr(dout), L.ptr(score), L.ptr(dx),
-                                               L.stream()))
-        return score, dx
-
-    def search(self, x, target, raw_mask, lam1, lam2, N, lr=0.2, betas=(0.9, 0.999), eps=1e-8,
-               state=None, want_traj=True, mode="freeze"):
-        x = self._clip(x)
-        b = x.shape[0]
-        T = self.clip_shape[1]
-        tgt = self._targets(target, b)
-        L.require_gpu(raw_mask)
-        if raw_mask.dtype != torch.float32 or not raw_mask.is_contiguous() or tuple(raw_mask.shape) != (b, T):
-            raise L.IvfError("raw_mask must be a contiguous float32 [b,T] tensor")
-        if state is None:
-            state = (torch.zeros_like(raw_mask), torch.zeros_like(raw_mask), 0)
-        m, v, done = state
-        traj = torch.empty(N, b, 4, device=self.device) if want_traj else None
-        with torch.cuda.device(self.device):
-            L.check(L.lib().ivf_clstm_search(self._h, L.ptr(x), b, L.ptr(tgt), L.ptr(raw_mask), L.ptr(m), L.ptr(v),
-                                             lam1, lam2, lr, betas[0], betas[1], eps, int(N), done + 1,
-                                             _mode_id(mode), L.ptr(traj), L.stream()))
-        return traj, (m, v, done + int(N))
-
-    def perturbed_forward(self, x, mask, mode="freeze"):
-        x = self._clip(x)
-        b = x.shape[0]
-        mask = L.f32c(mask.to(self.device))
-        if tuple(mask.shape) != (b, self.clip_shape[1]):
-            raise L.IvfError("mask must be [b,T]")
-        probs = torch.empty(b, self.K, device=self.device)
-        with torch.cuda.device(self.device):
-            L.check(L.lib().ivf_clstm_perturbed_forward(self._h, L.ptr(x), b, L.ptr(mask),
-                                                        _mode_id(mode), L.ptr(probs), L.stream()))
-        return probs
-
-    def blob_scores(self, x, target, max_len=None, mode="freeze"):
-        """I3DEngine.blob_scores with the ConvLSTM backbone (ivf_clstm_blob_scores)."""
-        return _blob_scores(self, L.lib().ivf_clstm_blob_scores, x, target, max_len, mode)
+        return super().backward(b, target, dout, True)      # this plan always writes dx
 
     # ------------------------------------------------------------ Grad-CAM
     def _cam_layer(self, layer):
@@ -494,19 +433,19 @@ class CLSTMEngine:
         return out
 
 
-class TFCLSTMEngine:
+class TFCLSTMEngine(_Engine):
     """SURVEY 8f N4, a DOCUMENTED EXTENSION (parity unpinned): the TF half's Keras ConvLSTM2D classifier
     (video_features_tf/models/clstm.py:87-126) and its temporal-mask search / per-frame Grad-CAM
     (mask/find_mask_kth.py:300-452, mask/gradcam.py:28-111) on libivf_hip's generic direct-convolution kernels
-    (csrc/tf_clstm.hip).  Clips are NCTHW like everywhere else; `from_tf_layout` converts [B,T,H,W,C]."""
+    (csrc/tf_clstm.hip).  Clips are NCTHW like everywhere else; `from_tf_layout` converts [B,T,H,W,C].
+    The plan perturbs by freezing only and has no one-blob entry (the inherited `blob_scores` finds no symbol)."""
+    _prefix = "tfclstm"
+    _has_mode = False
 
     def __init__(self, num_classes, clip_shape, units=(32, 32), kernel=(3, 5), stride=2, padding="valid",
                  recurrent_activation="hard_sigmoid", only_last_element_for_fc=True, max_batch=1, device=None):
-        L.require_gpu()
-        self.device = torch.device(device if device is not None else "cuda")
-        C, T, H, W = clip_shape
+        super().__init__(num_classes, clip_shape, max_batch, device)
         cfg = L.TFCLSTMConfig()
-        cfg.B, cfg.C, cfg.T, cfg.H, cfg.W = int(max_batch), C, T, H, W
         cfg.layers = len(units)
         for i, u in enumerate(units):
             cfg.units[i] = int(u)
@@ -519,21 +458,8 @@ class TFCLSTMEngine:
             raise L.IvfError("recurrent_activation must be 'hard_sigmoid' or 'sigmoid'")
         cfg.recurrent_hard_sigmoid = 1 if recurrent_activation == "hard_sigmoid" else 0
         cfg.only_last = 1 if only_last_element_for_fc else 0
-        cfg.num_classes = int(num_classes)
-        self.cfg, self.clip_shape, self.max_batch, self.K = cfg, (C, T, H, W), int(max_batch), int(num_classes)
         self.units = tuple(int(u) for u in units)
-        self._h = c_void_p()
-        L.check(L.lib().ivf_tfclstm_create(byref(cfg), byref(self._h)))
-        with torch.cuda.device(self.device):
-            self._weights = _arena(L.lib().ivf_tfclstm_weights_bytes(self._h), self.device)
-            self._ws = _arena(L.lib().ivf_tfclstm_workspace_bytes(self._h), self.device)
-        L.check(L.lib().ivf_tfclstm_bind(self._h, L.ptr(self._weights), L.ptr(self._ws)))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value and L is not None and getattr(L, "_lib", None) is not None:
-            L._lib.ivf_tfclstm_destroy(h)
-            self._h = c_void_p()
+        self._create(cfg)
 
     @staticmethod
     def from_tf_layout(x_bthwc):
@@ -564,18 +490,6 @@ class TFCLSTMEngine:
             L.check(L.lib().ivf_tfclstm_load_head(self._h, L.ptr(dw), L.ptr(db), L.stream()))
             torch.cuda.current_stream().synchronize()
 
-    _clip = I3DEngine._clip
-    _targets = I3DEngine._targets
-
-    def forward(self, x, want_logits=False):
-        x = self._clip(x)
-        b = x.shape[0]
-        probs = torch.empty(b, self.K, device=self.device)
-        logits = torch.empty(b, self.K, device=self.device) if want_logits else None
-        with torch.cuda.device(self.device):
-            L.check(L.lib().ivf_tfclstm_forward(self._h, L.ptr(x), b, L.ptr(logits), L.ptr(probs), L.stream()))
-        return (probs, logits) if want_logits else probs
-
     def backward(self, b, target):
         C, T, H, W = self.clip_shape
         tgt = self._targets(target, b)
@@ -586,28 +500,10 @@ class TFCLSTMEngine:
         return score, dx
 
     def perturbed_forward(self, x, mask):
-        x = self._clip(x)
-        b = x.shape[0]
-        mask = L.f32c(mask.to(self.device))
-        probs = torch.empty(b, self.K, device=self.device)
-        with torch.cuda.device(self.device):
-            L.check(L.lib().ivf_tfclstm_perturbed_forward(self._h, L.ptr(x), b, L.ptr(mask), L.ptr(probs), L.stream()))
-        return probs
+        return super().perturbed_forward(x, mask)
 
     def search(self, x, target, raw_mask, lam1, lam2, N, lr=0.2, betas=(0.9, 0.999), eps=1e-8, state=None):
-        x = self._clip(x)
-        b, T = x.shape[0], self.clip_shape[1]
-        tgt = self._targets(target, b)
-        if raw_mask.dtype != torch.float32 or not raw_mask.is_contiguous() or tuple(raw_mask.shape) != (b, T):
-            raise L.IvfError("raw_mask must be a contiguous float32 [b,T] tensor")
-        if state is None:
-            state = (torch.zeros_like(raw_mask), torch.zeros_like(raw_mask), 0)
-        m, v, done = state
-        traj = torch.empty(N, b, 4, device=self.device)
-        with torch.cuda.device(self.device):
-            L.check(L.lib().ivf_tfclstm_search(self._h, L.ptr(x), b, L.ptr(tgt), L.ptr(raw_mask), L.ptr(m), L.ptr(v), lam1, lam2,
-                                               lr, betas[0], betas[1], eps, int(N), done + 1, L.ptr(traj), L.stream()))
-        return traj, (m, v, done + int(N))
+        return super().search(x, target, raw_mask, lam1, lam2, N, lr, betas, eps, state)
 
     def gradcam(self, x, target, mask=None, normalization_mode="frame", out_hw=None):
         """mask/gradcam.py: per-frame maps [b,T,H,W]; normalization_mode 'frame' | 'sequence' (FLAGS.normalization_mode)."""

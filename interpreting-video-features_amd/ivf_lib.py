@@ -142,10 +142,7 @@ _SIGS = {
                                           POINTER(ctypes.c_double), POINTER(c_int), _I]),
     "ivf_i3d_num_sites": (c_int, [_P]),
     "ivf_i3d_site_name": (c_int, [_P, _I, c_char_p]),
-}
-
-# csrc/convlstm.hip
-_SIGS_OPT = {
+    # csrc/convlstm.hip
     "ivf_clstm_create": (c_int, [POINTER(CLSTMConfig), POINTER(c_void_p)]),
     "ivf_clstm_destroy": (None, [_P]),
     "ivf_clstm_weights_bytes": (c_size_t, [_P]),
@@ -198,16 +195,12 @@ def lib():
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in _SIGS_OPT.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
         _lib = L
     return _lib
 
 
 def exported_symbols():
-    return ["ivf_last_error"] + list(_SIGS) + list(_SIGS_OPT)
+    return ["ivf_last_error"] + list(_SIGS)
 
 
 def check(rc):
