@@ -398,7 +398,7 @@ __global__ void pack_fwd_kernel(const float* __restrict__ w, float* __restrict__
 // Wb[ci][(tapf)*Cout + co] = scale[co] * W[co][ci][kT-1-kt][kH-1-kh][kW-1-kw]
 // 1x1x1 units of one Inception module packed side by side for a single backward GEMM:
 // out[ci][koff + co] = scale[co] * w[co][ci], rows of length ldw (columns outside [koff,koff+Cout)
-// belong to the other units or are padding zeroed by the first unit, koff == 0).
+// belong to the other units or are row padding, zeroed by the unit that ends at ktotal).
 __global__ void pack_bwd_fused1x1_kernel(const float* __restrict__ w, const float* __restrict__ scale,
                                          float* __restrict__ out, int Cout, int Cin, int CinRows, int koff,
                                          int ktotal, int ldw, int math) {
