@@ -19,8 +19,6 @@
 // staged global -> registers -> LDS ([rows][32+4] floats: the +4 pad makes the
 // ds_read_b128 fragment reads conflict-free), the next chunk's global loads are
 // in flight while the current chunk's MFMAs run.
-#include <cstdlib>
-
 #include "conv_common.h"
 
 namespace ivf {
@@ -687,7 +685,6 @@ extern "C" int ivf_conv3d(const ivf_conv3d_desc* d, const float* in, const float
     IVF_CHECK_ARG(d->out_coff + d->Cout <= d->out_ld, "conv3d: output window outside ld");
   }
   if (d->math == 0) IVF_CHECK_ARG(a.ldw == a.K, "conv3d: internal ldw");
-  static const bool no_halo = getenv("IVF_NO_HALO") != nullptr;   // A/B switch for measurements
   const bool bf = d->math != IVF_MATH_FP32;
   // bf16act: which kernels can serve the two mixed-storage ends of the network
   const bool act_stem = d->math == IVF_MATH_BF16ACT && conv_pix4_supported(a);   // fp32 pixels in: pix4 only
@@ -710,9 +707,9 @@ extern "C" int ivf_conv3d(const ivf_conv3d_desc* d, const float* in, const float
     IVF_CHECK_ARG(!d->out2 && !a.gbo, "conv3d: the pix4 kernel has no second output window / gate record");
     return conv_pix4_launch(a, d->math, IVF_CONV_PIX4, (hipStream_t)stream);
   }
-  if (bf && (!no_halo || act_d2s) && !d->out2 && conv_halo_supported(a)) return conv_halo_launch(a, d->math, (hipStream_t)stream);
+  if (bf && !d->out2 && conv_halo_supported(a)) return conv_halo_launch(a, d->math, (hipStream_t)stream);
   IVF_CHECK_ARG(!act_d2s, "conv3d: bf16act depth-to-space needs the LDS-halo kernel (stride-1 form, k <= 4, Cin %% 8 == 0)");
-  if (bf && !no_halo && !d->out2 && !a.gbo && conv_pix4_supported(a)) return conv_pix4_launch(a, d->math, IVF_CONV_PIX4, (hipStream_t)stream);
+  if (bf && !d->out2 && !a.gbo && conv_pix4_supported(a)) return conv_pix4_launch(a, d->math, IVF_CONV_PIX4, (hipStream_t)stream);
   return conv_launch(a, d->math, (hipStream_t)stream);
 }
 

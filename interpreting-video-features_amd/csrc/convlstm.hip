@@ -16,6 +16,7 @@
 // Weights (a few KB) are staged in LDS by every block.
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include <cstdlib>
@@ -73,58 +74,7 @@ __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-
 
 // One cell step for all clips: gates = Gx[t] + Wh * h[t-1]; state update; saves
 // S[b,t,{i,f,g,o,c},j,y,x] and H[b,t,j,y,x].
-__global__ __launch_bounds__(256) void clstm_step_fwd_kernel(
-    const float* __restrict__ gx, const float* __restrict__ whT, float* __restrict__ S, float* __restrict__ Hs,
-    int B, int T, int t, int hid, int k, int Ho, int Wo) {
-  const int G = 4 * hid;
-  const int pad = (k - 1) / 2;
-  const long plane = (long)Ho * Wo;
-  const long total = (long)B * plane;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    int xo = i % Wo;
-    int yo = (i / Wo) % Ho;
-    int b = i / plane;
-    const float* gp = gx + (((long)b * T + t) * G) * plane + (long)yo * Wo + xo;
-    float acc[16];
-#pragma unroll
-    for (int o = 0; o < 16; ++o) acc[o] = (o < G) ? gp[(long)o * plane] : 0.f;
-    if (t > 0) {
-      const float* hp = Hs + (((long)b * T + (t - 1)) * hid) * plane;
-      for (int c = 0; c < hid; ++c)
-        for (int ky = 0; ky < k; ++ky) {
-          int y = yo - pad + ky;
-          for (int kx = 0; kx < k; ++kx) {
-            int xx = xo - pad + kx;
-            float v = ((unsigned)y < (unsigned)Ho && (unsigned)xx < (unsigned)Wo)
-                          ? hp[(long)c * plane + (long)y * Wo + xx] : 0.f;
-            const float* wp = whT + ((c * k + ky) * k + kx) * 16;
-#pragma unroll
-            for (int o = 0; o < 16; ++o) acc[o] = __builtin_fmaf(wp[o], v, acc[o]);
-          }
-        }
-    }
-    float* sp = S + (((long)b * T + t) * 5 * hid) * plane + (long)yo * Wo + xo;
-    const float* cprev = (t > 0) ? S + ((((long)b * T + (t - 1)) * 5 + 4) * hid) * plane + (long)yo * Wo + xo : nullptr;
-    float* hp2 = Hs + (((long)b * T + t) * hid) * plane + (long)yo * Wo + xo;
-    for (int j = 0; j < hid; ++j) {
-      float ci = sigmoidf_(acc[j]);
-      float cf = sigmoidf_(acc[hid + j]);
-      float cg = tanhf(acc[2 * hid + j]);
-      float co = sigmoidf_(acc[3 * hid + j]);
-      float cp = cprev ? cprev[(long)j * plane] : 0.f;
-      float cc = cf * cp + ci * cg;
-      float ch = co * tanhf(cc);
-      sp[(long)(0 * hid + j) * plane] = ci;
-      sp[(long)(1 * hid + j) * plane] = cf;
-      sp[(long)(2 * hid + j) * plane] = cg;
-      sp[(long)(3 * hid + j) * plane] = co;
-      sp[(long)(4 * hid + j) * plane] = cc;
-      hp2[(long)j * plane] = ch;
-    }
-  }
-}
-
-// The same cell step with the hidden-state convolution split over the 4 waves of a workgroup by
+// The hidden-state convolution is split over the 4 waves of a workgroup by
 // input channel (hid <= 4): a workgroup owns 64 pixels, wave c accumulates the 25 taps of channel c
 // into all 16 gates (its weights stay wave-uniform scalar operands), the partial sums meet in LDS
 // and wave j finishes hidden channel j.  A quarter of the serial chain per thread: what the small
@@ -427,58 +377,7 @@ __global__ void clstm_unpool_bwd_kernel(const float* __restrict__ dX, const unsi
 // Backward cell step t (convolution_lstm.py:38-48 differentiated):
 // dh = dHpool[t] + Wh^T (x) dG[t+1];  do = dh*tanh(c); dc = dh*o*(1-tanh^2 c) + dC;
 // di = dc*g; df = dc*c_prev; dg = dc*i; dC <- dc*f;  dG = gate derivatives.
-__global__ __launch_bounds__(256) void clstm_step_bwd_kernel(
-    const float* __restrict__ dHpool, const float* __restrict__ whB, const float* __restrict__ S,
-    float* __restrict__ dG, float* __restrict__ dC, int B, int T, int t, int hid, int k, int Ho, int Wo) {
-  const int G = 4 * hid;
-  const int pad = (k - 1) / 2;
-  const long plane = (long)Ho * Wo;
-  const long total = (long)B * plane;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    int x = i % Wo;
-    int y = (i / Wo) % Ho;
-    int b = i / plane;
-    float dh[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < hid; ++j) dh[j] = dHpool[(((long)b * T + t) * hid + j) * plane + (long)y * Wo + x];
-    if (t + 1 < T) {
-      const float* gp = dG + (((long)b * T + (t + 1)) * G) * plane;
-      for (int ky = 0; ky < k; ++ky) {
-        int yy = y - ky + pad;
-        for (int kx = 0; kx < k; ++kx) {
-          int xx = x - kx + pad;
-          const bool ok = (unsigned)yy < (unsigned)Ho && (unsigned)xx < (unsigned)Wo;
-          const float* wp = whB + (ky * k + kx) * 64;     // [o][j], j padded to 4
-#pragma unroll
-          for (int o = 0; o < 16; ++o) {
-            float g = (ok && o < G) ? gp[(long)o * plane + (long)yy * Wo + xx] : 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dh[j] = __builtin_fmaf(wp[o * 4 + j], g, dh[j]);
-          }
-        }
-      }
-    }
-    const float* sp = S + (((long)b * T + t) * 5 * hid) * plane + (long)y * Wo + x;
-    const float* cprev = (t > 0) ? S + ((((long)b * T + (t - 1)) * 5 + 4) * hid) * plane + (long)y * Wo + x : nullptr;
-    float* gout = dG + (((long)b * T + t) * G) * plane + (long)y * Wo + x;
-    float* dcp = dC + ((long)b * hid) * plane + (long)y * Wo + x;
-    for (int j = 0; j < hid; ++j) {
-      float ci = sp[(long)(0 * hid + j) * plane], cf = sp[(long)(1 * hid + j) * plane];
-      float cg = sp[(long)(2 * hid + j) * plane], co = sp[(long)(3 * hid + j) * plane];
-      float cc = sp[(long)(4 * hid + j) * plane];
-      float cp = cprev ? cprev[(long)j * plane] : 0.f;
-      float th = tanhf(cc);
-      float dco = dh[j] * th;
-      float dcc = dh[j] * co * (1.f - th * th) + ((t + 1 < T) ? dcp[(long)j * plane] : 0.f);
-      gout[(long)(0 * hid + j) * plane] = dcc * cg * (ci * (1.f - ci));
-      gout[(long)(1 * hid + j) * plane] = dcc * cp * (cf * (1.f - cf));
-      gout[(long)(2 * hid + j) * plane] = dcc * ci * (1.f - cg * cg);
-      gout[(long)(3 * hid + j) * plane] = dco * (co * (1.f - co));
-      dcp[(long)j * plane] = dcc * cf;
-    }
-  }
-}
-
-// Backward cell step split over the 4 waves of a workgroup by gate type (hid <= 4): wave g gathers
+// The step is split over the 4 waves of a workgroup by gate type (hid <= 4): wave g gathers
 // the taps of gates [g*hid, (g+1)*hid) of step t+1 into a partial dH (weights stay scalar operands),
 // the partials meet in LDS, wave j finishes hidden channel j.  Same reasoning as the forward split.
 __global__ __launch_bounds__(256) void clstm_step_bwd_split_kernel(
@@ -1148,6 +1047,18 @@ extern "C" int ivf_clstm_load_head(ivf_clstm_t* n, const float* bn_gamma, const 
 
 namespace ivf {
 
+// f(std::integral_constant<int, n>) for a run-time n of 1..4 (4 for anything else): the launches below whose kernels
+// take the hidden / input channel count as a template argument
+template <class F>
+static int with_const_1to4(int n, F&& f) {
+  switch (n) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
+}
+
 // The persistent recurrence (clstm_seq_*_kernel): hid <= 4, the clip's map within SEQ_MAXP pixels per thread and its
 // padded planes within the LDS; chosen for batches that fill the chip with one workgroup per clip
 // (IVF_CLSTM_PERSIST=1 always / 0 never: tests and A/B measurements).
@@ -1203,37 +1114,22 @@ static int clstm_run_forward(ivf_clstm* n, const float* x, int b, float* logits,
                          hid, k, c.stride, p.Ho, p.Wo);
     IVF_CHECK_LAUNCH();
     if (seq_ok(p, c, b)) {       // the whole recurrence of the layer in one launch, one workgroup per clip
-#define IVF_SEQ_F(HH)                                                                                                   \
-  {                                                                                                                      \
-    static LdsAttrOnce once;                                                                                             \
-    IVF_PROPAGATE(raise_lds_limit(reinterpret_cast<const void*>(&clstm_seq_fwd_kernel<HH>), 160 * 1024, once));          \
-    hipLaunchKernelGGL(clstm_seq_fwd_kernel<HH>, dim3(b), dim3(seq_threads(p)), seq_lds_bytes(p, c), s, n->wsf(p.gx_off), \
-                       n->wa + p.whT_off, n->wsf(p.S_off), n->wsf(p.H_off), T, k, p.Ho, p.Wo);                          \
-  }
-      switch (hid) {
-        case 1: IVF_SEQ_F(1) break;
-        case 2: IVF_SEQ_F(2) break;
-        case 3: IVF_SEQ_F(3) break;
-        default: IVF_SEQ_F(4) break;
-      }
-#undef IVF_SEQ_F
+      IVF_PROPAGATE(with_const_1to4(hid, [&](auto HH) -> int {
+        static LdsAttrOnce once;
+        IVF_PROPAGATE(raise_lds_limit(reinterpret_cast<const void*>(&clstm_seq_fwd_kernel<HH>), 160 * 1024, once));
+        hipLaunchKernelGGL(clstm_seq_fwd_kernel<HH>, dim3(b), dim3(seq_threads(p)), seq_lds_bytes(p, c), s, n->wsf(p.gx_off),
+                           n->wa + p.whT_off, n->wsf(p.S_off), n->wsf(p.H_off), T, k, p.Ho, p.Wo);
+        return IVF_OK;
+      }));
       IVF_CHECK_LAUNCH();
     } else
     for (int t = 0; t < T; ++t) {
-      if (hid > 4) {
+      if (hid > 4)
         hipLaunchKernelGGL(clstm_step_fwd_wide_kernel, dim3(grid_for((long)b * p.Ho * p.Wo, 256, 16384), hid / 4),
                            dim3(256), 0, s, n->wsf(p.gx_off), n->wa + p.whW_off, n->wsf(p.S_off), n->wsf(p.H_off), b, T,
                            t, hid, k, p.Ho, p.Wo);
-        IVF_CHECK_LAUNCH();
-        continue;
-      }
-      static const int split_below = getenv("IVF_CLSTM_SPLIT") ? atoi(getenv("IVF_CLSTM_SPLIT")) : (1 << 30);
-      if (hid <= 4 && (long)b * p.Ho * p.Wo <= split_below)
-        hipLaunchKernelGGL(clstm_step_fwd_split_kernel, dim3((unsigned)(((long)b * p.Ho * p.Wo + 63) / 64)), dim3(256), 0,
-                           s, n->wsf(p.gx_off), n->wa + p.whT_off, n->wsf(p.S_off), n->wsf(p.H_off), b, T, t, hid, k,
-                           p.Ho, p.Wo);
       else
-        hipLaunchKernelGGL(clstm_step_fwd_kernel, dim3(grid_for((long)b * p.Ho * p.Wo, 256, 16384)), dim3(256), 0,
+        hipLaunchKernelGGL(clstm_step_fwd_split_kernel, dim3((unsigned)(((long)b * p.Ho * p.Wo + 63) / 64)), dim3(256), 0,
                            s, n->wsf(p.gx_off), n->wa + p.whT_off, n->wsf(p.S_off), n->wsf(p.H_off), b, T, t, hid, k,
                            p.Ho, p.Wo);
       IVF_CHECK_LAUNCH();
@@ -1289,37 +1185,22 @@ static int clstm_run_backward(ivf_clstm* n, int b, const int* target, const floa
                        p.Ho, p.Wo, p.Hp, p.Wp);
     IVF_CHECK_LAUNCH();
     if (seq_ok(p, c, b)) {
-#define IVF_SEQ_B(HH)                                                                                                     \
-  {                                                                                                                        \
-    static LdsAttrOnce once;                                                                                               \
-    IVF_PROPAGATE(raise_lds_limit(reinterpret_cast<const void*>(&clstm_seq_bwd_kernel<HH>), 160 * 1024, once));            \
-    hipLaunchKernelGGL(clstm_seq_bwd_kernel<HH>, dim3(b), dim3(seq_threads(p)), seq_lds_bytes(p, c), s, n->wsf(p.dHp_off), \
-                       n->wa + p.whB_off, n->wsf(p.S_off), n->wsf(p.dG_off), n->wsf(p.dC_off), T, k, p.Ho, p.Wo);        \
-  }
-      switch (hid) {
-        case 1: IVF_SEQ_B(1) break;
-        case 2: IVF_SEQ_B(2) break;
-        case 3: IVF_SEQ_B(3) break;
-        default: IVF_SEQ_B(4) break;
-      }
-#undef IVF_SEQ_B
+      IVF_PROPAGATE(with_const_1to4(hid, [&](auto HH) -> int {
+        static LdsAttrOnce once;
+        IVF_PROPAGATE(raise_lds_limit(reinterpret_cast<const void*>(&clstm_seq_bwd_kernel<HH>), 160 * 1024, once));
+        hipLaunchKernelGGL(clstm_seq_bwd_kernel<HH>, dim3(b), dim3(seq_threads(p)), seq_lds_bytes(p, c), s, n->wsf(p.dHp_off),
+                           n->wa + p.whB_off, n->wsf(p.S_off), n->wsf(p.dG_off), n->wsf(p.dC_off), T, k, p.Ho, p.Wo);
+        return IVF_OK;
+      }));
       IVF_CHECK_LAUNCH();
     } else
     for (int t = T - 1; t >= 0; --t) {
-      static const int split_below = getenv("IVF_CLSTM_SPLIT") ? atoi(getenv("IVF_CLSTM_SPLIT")) : (1 << 30);
-      if (hid > 4) {
+      if (hid > 4)
         hipLaunchKernelGGL(clstm_step_bwd_wide_kernel, dim3(grid_for((long)b * p.Ho * p.Wo, 256, 16384), hid / 4),
                            dim3(256), 0, s, n->wsf(p.dHp_off), n->wa + p.whBW_off, n->wsf(p.S_off), n->wsf(p.dG_off),
                            n->wsf(p.dC_off), b, T, t, hid, k, p.Ho, p.Wo);
-        IVF_CHECK_LAUNCH();
-        continue;
-      }
-      if (hid <= 4 && (long)b * p.Ho * p.Wo <= split_below)
-        hipLaunchKernelGGL(clstm_step_bwd_split_kernel, dim3((unsigned)(((long)b * p.Ho * p.Wo + 63) / 64)), dim3(256), 0,
-                           s, n->wsf(p.dHp_off), n->wa + p.whB_off, n->wsf(p.S_off), n->wsf(p.dG_off),
-                           n->wsf(p.dC_off), b, T, t, hid, k, p.Ho, p.Wo);
       else
-        hipLaunchKernelGGL(clstm_step_bwd_kernel, dim3(grid_for((long)b * p.Ho * p.Wo, 256, 16384)), dim3(256), 0,
+        hipLaunchKernelGGL(clstm_step_bwd_split_kernel, dim3((unsigned)(((long)b * p.Ho * p.Wo + 63) / 64)), dim3(256), 0,
                            s, n->wsf(p.dHp_off), n->wa + p.whB_off, n->wsf(p.S_off), n->wsf(p.dG_off),
                            n->wsf(p.dC_off), b, T, t, hid, k, p.Ho, p.Wo);
       IVF_CHECK_LAUNCH();
@@ -1338,16 +1219,11 @@ static int clstm_run_backward(ivf_clstm* n, int b, const int* target, const floa
         sT % 2 == 0 && sB % 2 == 0)
     {
       const dim3 grid(grid_for((long)b * T * (p.Hin / 2) * (p.Win / 2), 256, 16384));
-#define IVF_XB(CI)                                                                                              \
-  hipLaunchKernelGGL(clstm_xconv_bwd_k5s2_kernel<CI>, grid, dim3(256), 0, s, n->wsf(p.dG_off), n->wa + p.wxB_off, \
-                     out, b, T, p.cin, p.Hin, p.Win, sB, sC, sT, hid, p.Ho, p.Wo)
-      switch (p.cin) {
-        case 1: IVF_XB(1); break;
-        case 2: IVF_XB(2); break;
-        case 3: IVF_XB(3); break;
-        default: IVF_XB(4); break;
-      }
-#undef IVF_XB
+      with_const_1to4(p.cin, [&](auto CI) -> int {
+        hipLaunchKernelGGL(clstm_xconv_bwd_k5s2_kernel<CI>, grid, dim3(256), 0, s, n->wsf(p.dG_off), n->wa + p.wxB_off,
+                           out, b, T, p.cin, p.Hin, p.Win, sB, sC, sT, hid, p.Ho, p.Wo);
+        return IVF_OK;
+      });
     }
     else if (hid > 4)
       hipLaunchKernelGGL(clstm_xconv_bwd_wide_kernel,

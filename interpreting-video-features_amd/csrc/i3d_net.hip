@@ -347,9 +347,8 @@ static int build_plan(ivf_i3d* n) {
       const ActBuf& d = n->bufs[o.dst];
       o.idx_off = takeb(B * d.per_clip());
     }
-  static const bool no_gate_bits = getenv("IVF_NO_GATE_BITS") != nullptr;   // A/B switch for measurements
   for (const auto& o : n->ops)
-    if (o.type == Op::CONV && !o.bwd_skip && o.bwd_mask && (n->bufs[o.src].C & 7) == 0 && !no_gate_bits)
+    if (o.type == Op::CONV && !o.bwd_skip && o.bwd_mask && (n->bufs[o.src].C & 7) == 0)
       n->bufs[o.src].need_gate = true;
   // every producer of such a buffer must be able to record the bits: an implicit-GEMM / LDS-halo epilogue writing
   // an 8-aligned channel window (the stem's pix4 kernel and the pools cannot)

@@ -5,8 +5,6 @@
 //
 // Reference: MaxPool3dSamePadding (models/I3D_doubled.py:8-40), head
 // (I3D_doubled.py:360-380), GradCamVideo.__call__ (grad_cam_videos.py:85-140).
-#include <cstdlib>
-
 #include "ivf_common.h"
 
 namespace ivf {
@@ -455,176 +453,6 @@ static bool launch_pool_bwd_fixed16(const PoolArgs& a, const T* dy, const unsign
   return true;
 }
 
-// ---------------------------------------------------------------- LDS-tiled max-pool
-// The direct kernels above re-read every input (forward) or every (dY, arg-max) pair
-// (backward) once per window that covers it -- up to 27x through L1/L2.  The tiled forms
-// stage the needed region of one 32-channel slab in LDS once (coalesced 128-byte rows) and
-// run the same window scan / gather against LDS, so global traffic is ~1x the tensors.
-constexpr int POOL_SLAB = 16;       // channels per workgroup
-constexpr int POOL_ROW = POOL_SLAB + 4;   // floats per LDS row (pad: conflict-free 16-byte reads)
-
-struct PoolTile {
-  int tT, tH, tW;      // tile of outputs (forward) / inputs (backward) per workgroup
-  int rT, rH, rW;      // staged region extents
-  int nT, nH, nW;      // tiles per dim
-  int slabs;
-};
-
-template <class T>
-__global__ __launch_bounds__(256) void maxpool_fwd_tiled_kernel(const T* __restrict__ x, T* __restrict__ y,
-                                                                unsigned char* __restrict__ idx, PoolArgs a,
-                                                                PoolTile t) {
-  extern __shared__ __attribute__((aligned(16))) float sx[];   // [rT*rH*rW][POOL_ROW]
-  int blk = xcd_remap(blockIdx.x, gridDim.x);   // neighbouring tiles (shared halo rows) on one XCD, i.e. one L2
-  const int slab = blk % t.slabs; blk /= t.slabs;
-  const int iw = blk % t.nW; blk /= t.nW;
-  const int ih = blk % t.nH; blk /= t.nH;
-  const int it = blk % t.nT;
-  const int b = blk / t.nT;
-  const int o_t0 = it * t.tT, o_h0 = ih * t.tH, o_w0 = iw * t.tW;
-  const int i_t0 = o_t0 * a.sT - a.pT, i_h0 = o_h0 * a.sH - a.pH, i_w0 = o_w0 * a.sW - a.pW;
-  const int c0 = slab * POOL_SLAB;
-  const int nreg = t.rT * t.rH * t.rW;
-  // stage: 8 float4 per position, zero fill outside the tensor (zero padding) and beyond C
-  for (int i = threadIdx.x; i < nreg * (POOL_SLAB / 4); i += blockDim.x) {
-    int g = i % (POOL_SLAB / 4), r = i / (POOL_SLAB / 4);
-    int rw = r % t.rW;
-    int r2 = r / t.rW;
-    int rh = r2 % t.rH;
-    int rt = r2 / t.rH;
-    int ti = i_t0 + rt, hi = i_h0 + rh, wi = i_w0 + rw;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if ((unsigned)ti < (unsigned)a.Ti && (unsigned)hi < (unsigned)a.Hi && (unsigned)wi < (unsigned)a.Wi &&
-        c0 + 4 * g < a.C)
-      v = ld4(x + ((size_t)((b * a.Ti + ti) * a.Hi + hi) * a.Wi + wi) * a.in_ld +
-                                           a.in_coff + c0 + 4 * g);
-    *reinterpret_cast<float4*>(&sx[r * POOL_ROW + 4 * g]) = v;
-  }
-  __syncthreads();
-  const int nout = t.tT * t.tH * t.tW;
-  for (int i = threadIdx.x; i < nout * (POOL_SLAB / 4); i += blockDim.x) {
-    int g = i % (POOL_SLAB / 4), o = i / (POOL_SLAB / 4);
-    int ow = o % t.tW;
-    int o2 = o / t.tW;
-    int oh = o2 % t.tH;
-    int ot = o2 / t.tH;
-    int to = o_t0 + ot, ho = o_h0 + oh, wo = o_w0 + ow;
-    if (to >= a.To || ho >= a.Ho || wo >= a.Wo || c0 + 4 * g >= a.C) continue;
-    float best[4];
-    int bi[4];
-    int tap = 0;
-    for (int kt = 0; kt < a.kT; ++kt)
-      for (int kh = 0; kh < a.kH; ++kh)
-        for (int kw = 0; kw < a.kW; ++kw, ++tap) {
-          int r = ((ot * a.sT + kt) * t.rH + oh * a.sH + kh) * t.rW + ow * a.sW + kw;
-          float4 v = *reinterpret_cast<const float4*>(&sx[r * POOL_ROW + 4 * g]);
-          float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            if (tap == 0 || vv[q] > best[q] || vv[q] != vv[q]) { best[q] = vv[q]; bi[q] = tap; }
-        }
-    size_t m = ((size_t)(b * a.To + to) * a.Ho + ho) * a.Wo + wo;
-    st4(y + m * a.out_ld + a.out_coff + c0 + 4 * g, make_float4(best[0], best[1], best[2], best[3]));
-    if (idx) {
-      if (a.dead)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (!(best[q] > 0.f)) bi[q] = 255;
-      *reinterpret_cast<uchar4*>(idx + m * a.C + c0 + 4 * g) = make_uchar4(bi[0], bi[1], bi[2], bi[3]);
-    }
-  }
-}
-
-template <class T>
-__global__ __launch_bounds__(256) void maxpool_bwd_tiled_kernel(const T* __restrict__ dy,
-                                                                const unsigned char* __restrict__ idx,
-                                                                T* __restrict__ dx,
-                                                                const T* __restrict__ relu_mask,
-                                                                int accumulate, PoolArgs a, PoolTile t, int o_lo_t,
-                                                                int o_lo_h, int o_lo_w) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];   // dY region [n][POOL_ROW] floats, then arg-max bytes
-  int blk = xcd_remap(blockIdx.x, gridDim.x);   // neighbouring tiles (shared halo rows) on one XCD, i.e. one L2
-  const int slab = blk % t.slabs; blk /= t.slabs;
-  const int iw = blk % t.nW; blk /= t.nW;
-  const int ih = blk % t.nH; blk /= t.nH;
-  const int it = blk % t.nT;
-  const int b = blk / t.nT;
-  const int i_t0 = it * t.tT, i_h0 = ih * t.tH, i_w0 = iw * t.tW;
-  // first output index whose window can cover the tile's first input: ceil((i0 + p - k + 1)/s), clipped later
-  auto first_out = [](int i0, int p, int k, int s) { int n = i0 + p - k + s; return n >= 0 ? n / s : -((-n + s - 1) / s); };
-  const int r_t0 = first_out(i_t0, a.pT, a.kT, a.sT), r_h0 = first_out(i_h0, a.pH, a.kH, a.sH),
-            r_w0 = first_out(i_w0, a.pW, a.kW, a.sW);
-  (void)o_lo_t; (void)o_lo_h; (void)o_lo_w;
-  const int c0 = slab * POOL_SLAB;
-  const int nreg = t.rT * t.rH * t.rW;
-  unsigned char* si = reinterpret_cast<unsigned char*>(sm + (size_t)nreg * POOL_ROW);   // [nreg][POOL_SLAB]
-  for (int i = threadIdx.x; i < nreg * (POOL_SLAB / 4); i += blockDim.x) {
-    int g = i % (POOL_SLAB / 4), r = i / (POOL_SLAB / 4);
-    int rw = r % t.rW;
-    int r2 = r / t.rW;
-    int rh = r2 % t.rH;
-    int rt = r2 / t.rH;
-    int to = r_t0 + rt, ho = r_h0 + rh, wo = r_w0 + rw;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    uchar4 u = make_uchar4(255, 255, 255, 255);   // matches no tap
-    if ((unsigned)to < (unsigned)a.To && (unsigned)ho < (unsigned)a.Ho && (unsigned)wo < (unsigned)a.Wo &&
-        c0 + 4 * g < a.C) {
-      size_t mo = ((size_t)(b * a.To + to) * a.Ho + ho) * a.Wo + wo;
-      v = ld4(dy + mo * a.out_ld + a.out_coff + c0 + 4 * g);
-      u = *reinterpret_cast<const uchar4*>(idx + mo * a.C + c0 + 4 * g);
-    }
-    *reinterpret_cast<float4*>(&sm[r * POOL_ROW + 4 * g]) = v;
-    *reinterpret_cast<uchar4*>(&si[r * POOL_SLAB + 4 * g]) = u;
-  }
-  __syncthreads();
-  const int nin = t.tT * t.tH * t.tW;
-  for (int i = threadIdx.x; i < nin * (POOL_SLAB / 4); i += blockDim.x) {
-    int g = i % (POOL_SLAB / 4), p = i / (POOL_SLAB / 4);
-    int pw = p % t.tW;
-    int p2 = p / t.tW;
-    int ph = p2 % t.tH;
-    int pt = p2 / t.tH;
-    int ti = i_t0 + pt, hi = i_h0 + ph, wi = i_w0 + pw;
-    if (ti >= a.Ti || hi >= a.Hi || wi >= a.Wi || c0 + 4 * g >= a.C) continue;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    const int nt = ti + a.pT, nh = hi + a.pH, nw = wi + a.pW;
-    const int t_hi = min(nt / a.sT, a.To - 1), t_lo = max((nt - a.kT + a.sT) / a.sT, 0);
-    const int h_hi = min(nh / a.sH, a.Ho - 1), h_lo = max((nh - a.kH + a.sH) / a.sH, 0);
-    const int w_hi = min(nw / a.sW, a.Wo - 1), w_lo = max((nw - a.kW + a.sW) / a.sW, 0);
-    for (int to = t_lo; to <= t_hi; ++to) {
-      const int kt = nt - to * a.sT;
-      for (int ho = h_lo; ho <= h_hi; ++ho) {
-        const int kh = nh - ho * a.sH;
-        for (int wo = w_lo; wo <= w_hi; ++wo) {
-          const int kw = nw - wo * a.sW;
-          const int tap = (kt * a.kH + kh) * a.kW + kw;
-          const int r = ((to - r_t0) * t.rH + (ho - r_h0)) * t.rW + (wo - r_w0);
-          uchar4 u = *reinterpret_cast<const uchar4*>(&si[r * POOL_SLAB + 4 * g]);
-          float4 gq = *reinterpret_cast<const float4*>(&sm[r * POOL_ROW + 4 * g]);
-          if (u.x == tap) acc[0] += gq.x;
-          if (u.y == tap) acc[1] += gq.y;
-          if (u.z == tap) acc[2] += gq.z;
-          if (u.w == tap) acc[3] += gq.w;
-        }
-      }
-    }
-    size_t m = ((size_t)(b * a.Ti + ti) * a.Hi + hi) * a.Wi + wi;
-    T* dst = dx + m * a.in_ld + a.in_coff + c0 + 4 * g;
-    if (accumulate) {
-      float4 o = ld4(dst);
-      acc[0] += o.x; acc[1] += o.y; acc[2] += o.z; acc[3] += o.w;
-    }
-    if (relu_mask) {
-      float4 k = ld4(relu_mask + m * a.in_ld + a.in_coff + c0 + 4 * g);
-      if (!(k.x > 0.f)) acc[0] = 0.f;
-      if (!(k.y > 0.f)) acc[1] = 0.f;
-      if (!(k.z > 0.f)) acc[2] = 0.f;
-      if (!(k.w > 0.f)) acc[3] = 0.f;
-    }
-    st4(dst, make_float4(acc[0], acc[1], acc[2], acc[3]));
-  }
-}
-
 // ---------------------------------------------------------------- 3x3x3 stride-1 'same' pools
 // The Inception branch pools (k 3, s 1, p 1).  One thread owns an image column (w, 4
 // channels) of a TH-row tile and walks the planes of the clip.  The window maximum is
@@ -932,29 +760,6 @@ static int pool_3s1_groups(const PoolArgs& a) {
   return G;
 }
 
-// tile choice: ~128-256 tile cells, staged region <= ~450 cells (<= 64 KB of LDS)
-static void pool_fwd_tile(const PoolArgs& a, PoolTile* t) {
-  t->tT = a.kT == 1 ? 1 : (a.sT == 1 ? 2 : 2);
-  t->tH = a.sH == 1 ? 8 : 8;
-  t->tW = a.sW == 1 ? 8 : 8;
-  if (a.sH == 2 && a.kT > 1) { t->tH = 4; t->tW = 4; }
-  t->rT = (t->tT - 1) * a.sT + a.kT;
-  t->rH = (t->tH - 1) * a.sH + a.kH;
-  t->rW = (t->tW - 1) * a.sW + a.kW;
-  t->nT = cdiv(a.To, t->tT); t->nH = cdiv(a.Ho, t->tH); t->nW = cdiv(a.Wo, t->tW);
-  t->slabs = cdiv(a.C, POOL_SLAB);
-}
-static void pool_bwd_tile(const PoolArgs& a, PoolTile* t) {
-  t->tT = a.kT == 1 ? 1 : (a.sT == 1 ? 2 : 4);
-  t->tH = a.sH == 1 ? 8 : 16;
-  t->tW = a.sW == 1 ? 8 : 16;
-  if (a.sH == 2 && a.kT > 1) { t->tH = 8; t->tW = 8; }
-  auto span = [](int tile, int k, int s) { return (tile + k - 2) / s + 1; };   // max #outputs covering `tile` inputs
-  t->rT = span(t->tT, a.kT, a.sT); t->rH = span(t->tH, a.kH, a.sH); t->rW = span(t->tW, a.kW, a.sW);
-  t->nT = cdiv(a.Ti, t->tT); t->nH = cdiv(a.Hi, t->tH); t->nW = cdiv(a.Wi, t->tW);
-  t->slabs = cdiv(a.C, POOL_SLAB);
-}
-
 // ---------------------------------------------------------------- head
 // One block per clip.  pooled[c] = mean over the npos feature cells;
 // logits[k] = bias[k] + sum_c pooled[c] W[k][c]; probs = softmax(logits).
@@ -1223,17 +1028,26 @@ static PoolArgs to_args(const ivf_pool3d_desc* d) {
 
 using namespace ivf;
 
+// The strided windows of the I3D variants (I3D_doubled.py:272-300; temporal stride 1 or 2), stated once: the fixed
+// forward is specialised by the window alone, the fixed backwards by window and stride.  f(window) launches if the
+// descriptor matches; the first match ends the walk.
+template <int KT, int KH, int KW, int ST, int SH, int SW>
+struct PoolWin { static constexpr int kT = KT, kH = KH, kW = KW, sT = ST, sH = SH, sW = SW; };
+template <class F>
+static bool any_fixed_pool(F&& f) {
+  return f(PoolWin<1, 3, 3, 1, 2, 2>{}) || f(PoolWin<3, 3, 3, 2, 2, 2>{}) || f(PoolWin<3, 3, 3, 1, 2, 2>{}) ||
+         f(PoolWin<2, 2, 2, 2, 2, 2>{}) || f(PoolWin<2, 2, 2, 1, 2, 2>{});
+}
+
+// Forward, three cases (figures: DESIGN section 7, "Pools", Mixed_3c / MaxPool3d_2a at B=64):
+//  1. 3x3x3 stride-1 'same' (the Inception branch pools), W <= 256: the separable kernel, 27/7 loads per output
+//     (fp32 513 us, bf16 450 us);
+//  2. a strided window of the table: the fixed-window kernel, 16 bytes per lane, every tap requested up front
+//     (fp32 473 -> 387 us = 5.6 TB/s of its compulsory bytes, bf16 414 -> 218 us);
+//  3. anything else, or channel geometry that is no multiple of the 16-byte lane: the generic kernel.
 template <class T>
 static int pool_fwd_impl(const PoolArgs& a, const T* x, T* y, unsigned char* argmax, hipStream_t stream) {
-  static const bool direct = getenv("IVF_POOL_DIRECT") != nullptr;   // A/B switch for measurements
-  PoolTile t;
-  pool_fwd_tile(a, &t);
-  size_t shm = (size_t)t.rT * t.rH * t.rW * POOL_ROW * sizeof(float);
-  // measured on MI355X (16-channel slabs): the tiled form wins 1.4x for the stride-1 3x3x3
-  // Inception pools (the direct kernel saturates L2 with its 27x re-reads) and loses for the
-  // strided pools, whose windows barely overlap
-  static const bool no_s1 = getenv("IVF_POOL_NO_S1") != nullptr;
-  if (!direct && !no_s1 && pool_is_3s1(a) && a.Wi <= 256) {
+  if (pool_is_3s1(a) && a.Wi <= 256) {
     const int G = pool_3s1_groups(a), nH = cdiv(a.Hi, S1_TH), slabs = cdiv(a.C, 4 * G);
     const int threads = ((a.Wi * G + 63) / 64) * 64;
     hipLaunchKernelGGL((maxpool3s1_fwd_kernel<T>), dim3((unsigned)(a.B * nH * slabs)), dim3(threads), 0, stream, x, y,
@@ -1241,21 +1055,12 @@ static int pool_fwd_impl(const PoolArgs& a, const T* x, T* y, unsigned char* arg
     IVF_CHECK_LAUNCH();
     return IVF_OK;
   }
-  const bool tiled_fwd = a.sT == 1 && a.sH == 1 && a.sW == 1;
-  if (!direct && tiled_fwd && shm <= 64 * 1024) {
-    long blocks = (long)a.B * t.nT * t.nH * t.nW * t.slabs;
-    hipLaunchKernelGGL((maxpool_fwd_tiled_kernel<T>), dim3((unsigned)blocks), dim3(256), shm, stream, x, y, argmax, a, t);
+  if ((a.sT > 1 || a.sH > 1 || a.sW > 1) && any_fixed_pool([&](auto w) {
+        using W = decltype(w);
+        return launch_pool_fwd_fixed<T, W::kT, W::kH, W::kW>(a, x, y, argmax, stream);
+      })) {
     IVF_CHECK_LAUNCH();
     return IVF_OK;
-  }
-  // the strided pools of the I3D variants with their windows known at compile time
-  static const bool no_fixed = getenv("IVF_POOL_NO_FIXED") != nullptr;
-  if (!direct && !no_fixed && (a.sT > 1 || a.sH > 1 || a.sW > 1)) {
-    if (launch_pool_fwd_fixed<T, 1, 3, 3>(a, x, y, argmax, stream) || launch_pool_fwd_fixed<T, 3, 3, 3>(a, x, y, argmax, stream) ||
-        launch_pool_fwd_fixed<T, 2, 2, 2>(a, x, y, argmax, stream)) {
-      IVF_CHECK_LAUNCH();
-      return IVF_OK;
-    }
   }
   const long nbx = cdiv((long)a.Wo * (a.C / 4), 256), nblk = nbx * a.Ho * a.B * a.To;
   IVF_CHECK_ARG(nblk < 0x7fffffffL, "maxpool_fwd: more than 2^31 workgroups");
@@ -1273,15 +1078,16 @@ extern "C" int ivf_maxpool3d_fwd(const ivf_pool3d_desc* d, const void* x, void* 
   return pool_fwd_impl<float>(a, (const float*)x, (float*)y, argmax, (hipStream_t)stream);
 }
 
+// Backward, the same three cases (figures: DESIGN section 7, "Pools" and item 10):
+//  1. 3x3x3 stride-1 'same', W <= 256: the separable gather (fp32 779 us, bf16 772 us on Mixed_3c's pool at B=64);
+//  2. a (window, stride) pair of the table: 2-byte storage with 8-aligned channel geometry takes the 16-byte-lane
+//     kernel (750 -> 538 us on MaxPool3d_2a), everything else the 4-channel one (fp32 measured faster in that form,
+//     827 vs 903 us; 4.5-4.7 TB/s of its compulsory bytes);
+//  3. anything else, or a grid beyond the launch limits: the generic grid-stride gather.
 template <class T>
 static int pool_bwd_impl(const PoolArgs& a, const T* dy, const unsigned char* argmax, T* dx, const T* relu_mask,
                          int accumulate, hipStream_t hs) {
-  static const bool direct = getenv("IVF_POOL_DIRECT") != nullptr;
-  PoolTile t;
-  pool_bwd_tile(a, &t);
-  size_t shm = (size_t)t.rT * t.rH * t.rW * (POOL_ROW * sizeof(float) + POOL_SLAB);
-  static const bool no_s1 = getenv("IVF_POOL_NO_S1") != nullptr;
-  if (!direct && !no_s1 && pool_is_3s1(a) && a.Wi <= 256) {
+  if (pool_is_3s1(a) && a.Wi <= 256) {
     const int G = pool_3s1_groups(a), slabs = cdiv(a.C, 4 * G);
     const int threads = ((a.Wi * G + 63) / 64) * 64;
     hipLaunchKernelGGL((maxpool3s1_bwd_kernel<T>), dim3((unsigned)(a.B * a.Hi * slabs)), dim3(threads), 0, hs, dy, argmax, dx,
@@ -1289,37 +1095,21 @@ static int pool_bwd_impl(const PoolArgs& a, const T* dy, const unsigned char* ar
     IVF_CHECK_LAUNCH();
     return IVF_OK;
   }
-  // the strided pools of the I3D variants (I3D_doubled.py:272-300; temporal strides 1 or 2)
-  static const bool no_fixed = getenv("IVF_POOL_NO_FIXED") != nullptr;
-  if (!direct && !no_fixed && (size_t)a.B * a.Ti * a.Hi * a.Wi * (a.C / 4) / 256 < 0x7fffffffu) {
-    if constexpr (sizeof(T) == 2) {   // 16-byte lanes, raw loads first
-      if (launch_pool_bwd_fixed16<T, 1, 3, 3, 1, 2, 2>(a, dy, argmax, dx, relu_mask, accumulate, hs) ||
-          launch_pool_bwd_fixed16<T, 3, 3, 3, 2, 2, 2>(a, dy, argmax, dx, relu_mask, accumulate, hs) ||
-          launch_pool_bwd_fixed16<T, 3, 3, 3, 1, 2, 2>(a, dy, argmax, dx, relu_mask, accumulate, hs) ||
-          launch_pool_bwd_fixed16<T, 2, 2, 2, 2, 2, 2>(a, dy, argmax, dx, relu_mask, accumulate, hs) ||
-          launch_pool_bwd_fixed16<T, 2, 2, 2, 1, 2, 2>(a, dy, argmax, dx, relu_mask, accumulate, hs)) {
-        IVF_CHECK_LAUNCH();
-        return IVF_OK;
-      }
-    }
-    if (launch_pool_bwd_fixed<T, 1, 3, 3, 1, 2, 2>(a, dy, argmax, dx, relu_mask, accumulate, hs) ||
-        launch_pool_bwd_fixed<T, 3, 3, 3, 2, 2, 2>(a, dy, argmax, dx, relu_mask, accumulate, hs) ||
-        launch_pool_bwd_fixed<T, 3, 3, 3, 1, 2, 2>(a, dy, argmax, dx, relu_mask, accumulate, hs) ||
-        launch_pool_bwd_fixed<T, 2, 2, 2, 2, 2, 2>(a, dy, argmax, dx, relu_mask, accumulate, hs) ||
-        launch_pool_bwd_fixed<T, 2, 2, 2, 1, 2, 2>(a, dy, argmax, dx, relu_mask, accumulate, hs)) {
+  if ((size_t)a.B * a.Ti * a.Hi * a.Wi * (a.C / 4) / 256 < 0x7fffffffu) {
+    bool launched = false;
+    if constexpr (sizeof(T) == 2)
+      launched = any_fixed_pool([&](auto w) {
+        using W = decltype(w);
+        return launch_pool_bwd_fixed16<T, W::kT, W::kH, W::kW, W::sT, W::sH, W::sW>(a, dy, argmax, dx, relu_mask, accumulate, hs);
+      });
+    launched = launched || any_fixed_pool([&](auto w) {
+      using W = decltype(w);
+      return launch_pool_bwd_fixed<T, W::kT, W::kH, W::kW, W::sT, W::sH, W::sW>(a, dy, argmax, dx, relu_mask, accumulate, hs);
+    });
+    if (launched) {
       IVF_CHECK_LAUNCH();
       return IVF_OK;
     }
-  }
-  // measured (16-channel slabs): the tiled gather wins 1.3-1.6x for every pool of the net
-  if (!direct && shm <= 80 * 1024) {
-    static LdsAttrOnce once;
-    IVF_PROPAGATE(raise_lds_limit(reinterpret_cast<const void*>(&maxpool_bwd_tiled_kernel<T>), 80 * 1024, once));
-    long blocks = (long)a.B * t.nT * t.nH * t.nW * t.slabs;
-    hipLaunchKernelGGL((maxpool_bwd_tiled_kernel<T>), dim3((unsigned)blocks), dim3(256), shm, hs, dy, argmax, dx, relu_mask,
-                       accumulate, a, t, 0, 0, 0);
-    IVF_CHECK_LAUNCH();
-    return IVF_OK;
   }
   size_t total = (size_t)a.B * a.Ti * a.Hi * a.Wi * (a.C / 4);
   hipLaunchKernelGGL((maxpool_bwd_kernel<T>), dim3(grid_for(total)), dim3(256), 0, hs, dy, argmax, dx, relu_mask, accumulate, a);

@@ -574,6 +574,60 @@ def test_maxpool_bf16_storage_equals_fp32_path(k, st, thw, C):
             assert torch.equal(acc, res['acc'].bfloat16())
 
 
+@pytest.mark.parametrize("k,st,thw", [((2, 3, 3), (1, 1, 1), (3, 5, 6)),      # stride 1, not cubic
+                                      ((1, 2, 2), (1, 2, 2), (3, 7, 6))])     # strided, off the fixed-window table
+def test_maxpool_generic_fallback_matches_torch(k, st, thw):
+    """Windows that no specialised pool kernel serves: by the three cases of pool_fwd_impl / pool_bwd_impl (3x3x3
+    stride-1, a strided window of the fixed table, anything else) these shapes can only reach maxpool_fwd_kernel /
+    maxpool_bwd_kernel.  fp32 storage against torch's CPU max_pool3d over the zero-padded input (TF-'same' padding,
+    I3D_doubled.py:8-40) on tie-rich, bf16-representable inputs: forward bit-exact, backward routing identical, then
+    accumulate + ReLU gate.  bf16 storage on the same tensors: same selection (values and arg-max), backward equal to
+    the fp32 result rounded once."""
+    import torch.nn.functional as F
+    import ivf_arch as arch
+    import ivf_lib as L
+    lib = L.lib()
+    gen = torch.Generator().manual_seed(9)
+    B, C = 2, 12
+    x = torch.relu(torch.round(torch.randn((B, C) + thw, generator=gen) * 3) / 3).bfloat16().float()
+    pads = [arch.same_pad(n, kk, ss) for n, kk, ss in zip(thw, k, st)]
+    outs = [arch.out_size(n, kk, ss) for n, kk, ss in zip(thw, k, st)]
+    gy = torch.randn((B, C) + tuple(outs), generator=gen).bfloat16().float()
+    xr = x.clone().requires_grad_()
+    y = F.max_pool3d(F.pad(xr, (pads[2][0], pads[2][1], pads[1][0], pads[1][1], pads[0][0], pads[0][1])), k, st)
+    assert list(y.shape[2:]) == outs
+    y.backward(gy)
+    ref = xr.grad.numpy()
+    base32 = torch.randn((B,) + thw + (C,), generator=gen).bfloat16().float()
+    res = {}
+    for bf in (False, True):
+        d, _ = _pool_desc(L, B, thw, C, k, st, bf)
+        dt = torch.bfloat16 if bf else torch.float32
+        xcl = to_cl(x.cuda(), C).to(dt)
+        gycl = to_cl(gy.cuda(), C).to(dt)
+        ycl = torch.full((B,) + tuple(outs) + (C,), float('nan'), dtype=dt, device='cuda')
+        idx = torch.full(ycl.shape, 0xEE, dtype=torch.uint8, device='cuda')     # neither a tap nor the dead code
+        L.check(lib.ivf_maxpool3d_fwd(ctypes.byref(d), L.ptr(xcl), L.ptr(ycl), L.ptr(idx), L.stream()))
+        dxcl = torch.full_like(xcl, float('nan'))
+        L.check(lib.ivf_maxpool3d_bwd(ctypes.byref(d), L.ptr(gycl), L.ptr(idx), L.ptr(dxcl), None, 0, L.stream()))
+        base = base32.to(dt).cuda()
+        acc = base.clone()
+        L.check(lib.ivf_maxpool3d_bwd(ctypes.byref(d), L.ptr(gycl), L.ptr(idx), L.ptr(acc), L.ptr(xcl), 1, L.stream()))
+        if not bf:
+            assert np.array_equal(from_cl(ycl, C).cpu().numpy(), y.detach().numpy())
+            assert bool((idx < k[0] * k[1] * k[2]).all())
+            dx = from_cl(dxcl, C).cpu().numpy()
+            assert np.array_equal(dx != 0, ref != 0)
+            assert np.allclose(dx, ref, rtol=1e-5, atol=1e-6)
+            want = torch.where(xcl > 0, base + dxcl, torch.zeros_like(base))
+            assert torch.allclose(acc, want, rtol=1e-6, atol=1e-6)
+            res = dict(y=ycl, idx=idx, dx=dxcl, acc=acc)
+        else:
+            assert torch.equal(ycl.float(), res['y']) and torch.equal(idx, res['idx'])
+            assert torch.equal(dxcl, res['dx'].bfloat16())
+            assert torch.equal(acc, res['acc'].bfloat16())
+
+
 @pytest.mark.parametrize("k,cin,cout,thw", [(3, 32, 40, (5, 15, 30)), (3, 16, 200, (3, 9, 15)), (1, 24, 72, (2, 5, 7)),
                                             (1, 64, 136, (4, 14, 14))])
 def test_every_conv_variant_bf16_activations(k, cin, cout, thw):

@@ -32,4 +32,4 @@ for name, (B, T, H, W, C, k, s) in cases.items():
         for _ in range(10): fn()
         e1.record(); torch.cuda.synchronize()
         ms = e0.elapsed_time(e1) / 10
-        print(f"{name:8s} {label} {ms*1e3:8.1f} us  {bytes_/ms/1e9:6.2f} TB/s (compulsory bytes)   no_fixed={os.environ.get('IVF_POOL_NO_FIXED','')}")
+        print(f"{name:8s} {label} {ms*1e3:8.1f} us  {bytes_/ms/1e9:6.2f} TB/s (compulsory bytes)")
