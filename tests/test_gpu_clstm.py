@@ -106,11 +106,16 @@ def test_clstm_other_geometries_match_oracle(C, T, H, W, hidden, kernel, stride)
                           effective_step=(T - 1,), add_softmax=True)
     y[0, 1].backward(retain_graph=True)
     g0 = xr.grad.clone()
+    xr.grad = None
+    y[1, 2].backward()                     # clip 1 has another target: its gradient is compared as well
+    g1 = xr.grad.clone()
     probs = eng.forward(x.cuda())
     assert rel_err(probs.cpu().numpy(), y.detach().numpy()) < 1e-3
     s, dx = eng.backward(B, target=[1, 2])
     assert abs(float(s[0]) - float(y[0, 1].detach())) < 1e-5
     assert rel_err(dx[0].cpu().numpy(), g0[0].numpy()) < 2e-3
+    assert abs(float(s[1]) - float(y[1, 2].detach())) < 1e-5
+    assert rel_err(dx[1].cpu().numpy(), g1[1].numpy()) < 2e-3
 
 
 def test_clstm_full_length_search(golden):
