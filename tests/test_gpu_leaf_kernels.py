@@ -43,6 +43,7 @@ def inside(got, ref, bound, what):
     err = (got.double().cpu() - ref).abs()
     bad = err > bound
     assert not bool(bad.any()), f"{what}: {int(bad.sum())} elements outside the bound, worst {float((err - bound).max()):.3e} over"
+    return err
 
 
 def dev_feat(feat, bf16):
