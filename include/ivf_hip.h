@@ -211,15 +211,20 @@ typedef struct {
   int gate_out_ld, gate_out_coff, gate_out2_ld, gate_in_ld, gate_in_coff;
 } ivf_conv3d_desc;
 
-/* Kernel variants: tile shapes of the plain implicit GEMM (IVF_CONV_IGEMM_BASE + 0..2) and of
- * the LDS-halo kernel (IVF_CONV_HALO_BASE + i; split-bf16, stride 1, 2 <= k <= 4 only).  All
- * variants compute the same sums; they differ in speed per layer shape and (in the last
- * bits) in summation order, so a plan fixes one variant per layer. */
+/* Kernel variants: the eight tile shapes of the plain implicit GEMM (IVF_CONV_IGEMM_BASE + 0..7: three
+ * narrow tiles for every arithmetic mode, three wide and two small ones for the split-bf16 modes), the
+ * 4-channel-pixel kernel (IVF_CONV_PIX4) and the tiles of the LDS-halo kernel (IVF_CONV_HALO_BASE + i;
+ * split-bf16, stride 1, 2 <= k <= 4 only).  All variants compute the same sums; they differ in speed
+ * per layer shape and (in the last bits) in summation order, so a plan fixes one variant per layer.
+ * ivf_conv3d_variants lists the candidates for a descriptor (one that this shape or arithmetic mode
+ * cannot run reports so when launched); ivf_conv3d_default_variant returns the id that IVF_CONV_AUTO
+ * runs, or a negative error. */
 #define IVF_CONV_AUTO 0
 #define IVF_CONV_IGEMM_BASE 1
 #define IVF_CONV_HALO_BASE 16
 #define IVF_CONV_PIX4 15 /* 4-channel-pixel strided kernel (the stem): split-bf16, Cin = in_ld = 4, stride (1|2, 2, 2), k <= 7 */
 int ivf_conv3d_variants(const ivf_conv3d_desc* d, int* ids, int max_ids);
+int ivf_conv3d_default_variant(const ivf_conv3d_desc* d);
 
 /* out = epilogue(conv(in, w_packed)): v = acc*scale[n] + shift[n] (NULL = 1 / 0);
  * relu_mask != NULL zeroes v where mask <= 0 (the ReLU below, for backward-data). */
@@ -602,7 +607,8 @@ int ivf_tfclstm_gradcam(ivf_tfclstm_t* net, const float* x, int b, const float* 
 /* ------------------------------------------------------------------ measurement */
 
 /* HIP-event timing of the convolution launches on their own stream, sampled on every
- * `every`-th iteration of ivf_*_search (bench.py's roofline leg).  collect: arrays of
+ * `every`-th iteration of ivf_*_search (bench.py's roofline leg; every = 0: on every launch, also
+ * of a direct ivf_conv3d call, which the tests of the dispatch use).  collect: arrays of
  * IVF_PROFILE_CLASSES entries indexed by kernel variant id (IVF_CONV_IGEMM_BASE + tile for
  * fp32, +3 for split-bf16; IVF_CONV_HALO_BASE + i): summed kernel milliseconds, launch count
  * and algorithmic FLOPs of the sampled launches. */

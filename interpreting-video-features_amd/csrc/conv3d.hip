@@ -496,25 +496,32 @@ static void launch_bf16(ConvKArgs& a, bool pw, dim3 grid, hipStream_t s) {
     hipLaunchKernelGGL((conv3d_igemm_bf16_kernel<AM, BM, BN, WM, WN, false>), grid, dim3(256), 0, s, a);
 }
 
-template <int BM, int BN, int WM, int WN>
+// The implicit-GEMM tiles (ivf_conv3d_desc.variant = IVF_CONV_IGEMM_BASE + index).  cls = profiler class of the
+// split-bf16 kernel (7..9 the wide tiles, 10..11 the small ones; the fp32 kernel of a narrow tile has class cls - 3).
+struct IgemmTile { int BM, BN, WM, WN, cls; bool bf16_only, fits_x6; };
+constexpr IgemmTile kIgemmTiles[8] = {
+    {128, 128, 2, 2, 4, false, true},
+    {128, 64, 4, 1, 5, false, true},
+    {128, 32, 4, 1, 6, false, true},
+    // wide tiles for the 1x1x1 convs (HBM-bound: the input rows are read once instead of once per 64-column tile)
+    {128, 256, 4, 1, 7, true, false},
+    {128, 192, 4, 1, 8, true, false},
+    {128, 160, 4, 1, 9, true, false},
+    // small tiles: twice the workgroups per CU for the latency-bound short-K GEMMs
+    {64, 64, 2, 2, 10, true, true},
+    {64, 128, 2, 2, 11, true, true},
+};
+
+// (variant_applicable has checked the tile against the arithmetic mode)
+template <int V>
 static int launch_variant(ConvKArgs& a, int math, hipStream_t s) {
+  constexpr IgemmTile t = kIgemmTiles[V];
+  constexpr int BM = t.BM, BN = t.BN, WM = t.WM, WN = t.WN;
+  static_assert(t.fits_x6 == ((3 * BM + 3 * BN) * LDS_ROW_BF * 2 <= 64 * 1024), "three operand planes in the static LDS");
   a.mtiles = cdiv(a.M, BM);
   a.ntiles = cdiv(a.Cout, BN);
   dim3 grid(a.mtiles * a.ntiles);
-  // profiler class: 1..3 fp32 tiles, 4..6 split-bf16 tiles, 7..9 the wide split-bf16 tiles, 10..11 the small ones
-  const int cls = BM == 64 ? (BN == 64 ? 10 : 11)
-                  : BN > 128 ? (BN == 256 ? 7 : (BN == 192 ? 8 : 9))
-                             : IVF_CONV_IGEMM_BASE + (BN == 128 ? 0 : (BN == 64 ? 1 : 2)) + (math ? 3 : 0);
-  constexpr bool wide = BN > 128 || BM == 64;          // split-bf16 only
-  constexpr bool fits_x6 = (3 * BM + 3 * BN) * LDS_ROW_BF * 2 <= 64 * 1024;
-  if (wide && math == IVF_MATH_FP32) {
-    set_error("conv3d: wide implicit-GEMM tiles exist for the split-bf16 modes only");
-    return IVF_ERR_UNSUPPORTED;
-  }
-  if (!fits_x6 && math == IVF_MATH_BF16X6) {
-    set_error("conv3d: this implicit-GEMM tile does not fit the LDS with three operand planes");
-    return IVF_ERR_UNSUPPORTED;
-  }
+  const int cls = math == IVF_MATH_FP32 ? t.cls - 3 : t.cls;
   if (math == IVF_MATH_FP32)
     prof_name(cls, "conv3d_igemm_kernel<%d,%d,%d,%d>", BM, BN, WM, WN);
   // a plain GEMM over the pixels: no taps, no strides, no padding
@@ -529,43 +536,31 @@ static int launch_variant(ConvKArgs& a, int math, hipStream_t s) {
               BM, BN, WM, WN, pw ? "true" : "false");
   const bool timed = prof_begin(s, cls);
   if (math == IVF_MATH_FP32) {
-    if constexpr (!wide) hipLaunchKernelGGL((conv3d_igemm_kernel<BM, BN, WM, WN>), grid, dim3(256), 0, s, a);
+    if constexpr (!t.bf16_only) hipLaunchKernelGGL((conv3d_igemm_kernel<BM, BN, WM, WN>), grid, dim3(256), 0, s, a);
   } else if (math == IVF_MATH_BF16X3) {
     launch_bf16<AM_X3, BM, BN, WM, WN>(a, pw, grid, s);
   } else if (math == IVF_MATH_BF16ACT) {
     launch_bf16<AM_BF16, BM, BN, WM, WN>(a, pw, grid, s);
   } else {
-    if constexpr (fits_x6) launch_bf16<AM_X6, BM, BN, WM, WN>(a, pw, grid, s);
+    if constexpr (t.fits_x6) launch_bf16<AM_X6, BM, BN, WM, WN>(a, pw, grid, s);
   }
   if (timed) prof_end(s);
   IVF_CHECK_LAUNCH();
   return IVF_OK;
 }
 
-int conv_launch(ConvKArgs& a, int math, hipStream_t s) {
-  // pick BN to minimise padded columns; ties go to the wider tile
+// built-in tile: the BN that minimises padded columns; ties go to the wider tile
+static int conv_igemm_default(const ConvKArgs& a) {
   int n128 = cdiv(a.Cout, 128) * 128, n64 = cdiv(a.Cout, 64) * 64, n32 = cdiv(a.Cout, 32) * 32;
-  if (n128 <= n64 && n128 <= n32) return launch_variant<128, 128, 2, 2>(a, math, s);
-  if (n64 <= n32) return launch_variant<128, 64, 4, 1>(a, math, s);
-  return launch_variant<128, 32, 4, 1>(a, math, s);
+  if (n128 <= n64 && n128 <= n32) return 0;
+  return n64 <= n32 ? 1 : 2;
 }
 
 int conv_igemm_launch_variant(ConvKArgs& a, int math, int v, hipStream_t s) {
-  switch (v) {
-    case 0: return launch_variant<128, 128, 2, 2>(a, math, s);
-    case 1: return launch_variant<128, 64, 4, 1>(a, math, s);
-    case 2: return launch_variant<128, 32, 4, 1>(a, math, s);
-    // wide tiles for the 1x1x1 convs (HBM-bound: the input rows are read once instead of once
-    // per 64-column tile)
-    case 3: return launch_variant<128, 256, 4, 1>(a, math, s);
-    case 4: return launch_variant<128, 192, 4, 1>(a, math, s);
-    case 5: return launch_variant<128, 160, 4, 1>(a, math, s);
-    // small tiles: twice the workgroups per CU for the latency-bound short-K GEMMs
-    case 6: return launch_variant<64, 64, 2, 2>(a, math, s);
-    case 7: return launch_variant<64, 128, 2, 2>(a, math, s);
-  }
-  set_error("conv3d: unknown implicit-GEMM variant %d", v);
-  return IVF_ERR_BAD_ARG;
+  static constexpr int (*launch[8])(ConvKArgs&, int, hipStream_t) = {
+      &launch_variant<0>, &launch_variant<1>, &launch_variant<2>, &launch_variant<3>,
+      &launch_variant<4>, &launch_variant<5>, &launch_variant<6>, &launch_variant<7>};
+  return launch[v](a, math, s);
 }
 
 static inline int pack_ldw(int K, int math) { return math ? (K + 7) / 8 * 8 : K; }
@@ -586,7 +581,8 @@ static void bwd_span(int k, int st, int pad, int* K, int* off) {
   *off = -dlo;
 }
 
-static int check_desc(const ivf_conv3d_desc* d) {
+// everything a descriptor must satisfy whichever kernel serves it (has_mask: a relu_mask pointer comes with it)
+static int check_desc(const ivf_conv3d_desc* d, bool has_mask) {
   IVF_CHECK_ARG(d != nullptr, "conv3d: null descriptor");
   IVF_CHECK_ARG(d->B > 0 && d->Ti > 0 && d->Hi > 0 && d->Wi > 0, "conv3d: bad input dims");
   IVF_CHECK_ARG(d->Cin > 0 && d->Cin % 4 == 0, "conv3d: Cin (%d) must be a positive multiple of 4", d->Cin);
@@ -603,19 +599,58 @@ static int check_desc(const ivf_conv3d_desc* d) {
   IVF_CHECK_ARG((long long)d->B * d->To * d->Ho * d->Wo < (1ll << 31) &&
                     (long long)d->B * d->Ti * d->Hi * d->Wi < (1ll << 31),
                 "conv3d: position count exceeds int32");
+  if (d->in2) {
+    IVF_CHECK_ARG(d->kT * d->kH * d->kW == 1, "conv3d: a second input is only defined for 1x1x1 convs");
+    IVF_CHECK_ARG(d->K0 > 0 && d->K0 < d->Cin && d->K0 % 4 == 0 && d->in2_ld % 4 == 0 && d->in2_coff % 4 == 0 &&
+                      d->in2_coff + (d->Cin - d->K0) <= d->in2_ld,
+                  "conv3d: second-input channel window must be 4-aligned inside its row");
+  }
+  if (d->out2) {
+    IVF_CHECK_ARG(!d->accumulate && !has_mask && !d->d2s,
+                  "conv3d: a second output window is a forward-epilogue feature (no accumulate / relu_mask / d2s)");
+    IVF_CHECK_ARG(d->N0 > 0 && d->N0 < d->Cout && d->out2_coff >= 0 && d->out2_coff + (d->Cout - d->N0) <= d->out2_ld &&
+                      d->out_coff + d->N0 <= d->out_ld,
+                  "conv3d: output windows [0,N0) / [N0,Cout) must fit their rows");
+  }
+  if (d->gate_out || d->gate_out2 || d->gate_in) {
+    IVF_CHECK_ARG(!d->d2s && (d->Cout & 7) == 0 && (d->out_ld & 3) == 0 && (d->out_coff & 3) == 0,
+                  "conv3d: 1-bit gates need Cout %% 8 == 0 and 4-aligned output rows (the 16-byte epilogue)");
+    IVF_CHECK_ARG(!d->out2 || ((d->N0 | d->out2_ld | d->out2_coff) & 3) == 0, "conv3d: 1-bit gates with out2 need 4-aligned windows");
+  }
+  if (d->gate_out || d->gate_out2) {
+    IVF_CHECK_ARG(!d->accumulate && !has_mask && !d->gate_in,
+                  "conv3d: gate_out / gate_out2 are forward-epilogue records (no accumulate / relu_mask / gate_in)");
+    IVF_CHECK_ARG(!d->gate_out || ((d->gate_out_coff & 7) == 0 && d->gate_out_ld > 0), "conv3d: gate_out window must be 8-aligned");
+    IVF_CHECK_ARG(!d->gate_out2 || (d->out2 && (d->N0 & 7) == 0 && (d->out2_coff & 7) == 0 && d->gate_out2_ld > 0),
+                  "conv3d: gate_out2 needs out2 with 8-aligned N0 / out2_coff");
+  }
+  if (d->gate_in)
+    IVF_CHECK_ARG(!has_mask && (d->gate_in_coff & 3) == 0 && d->gate_in_ld > 0,
+                  "conv3d: gate_in replaces relu_mask (give one of them) and needs a 4-aligned channel offset");
+  IVF_CHECK_ARG(d->math >= IVF_MATH_FP32 && d->math <= IVF_MATH_BF16ACT, "conv3d: math must be one of IVF_MATH_* (0..3)");
+  if (d->math == IVF_MATH_BF16ACT) {
+    // bf16 storage on both sides, except: the 4-channel-pixel strided conv reads fp32 pixels (pix4 kernel only), a
+    // depth-to-space backward writes fp32 (LDS-halo kernel only)
+    IVF_CHECK_ARG(!(d->d2s && (d->accumulate || d->relu)), "conv3d: bf16act depth-to-space output is a plain fp32 store");
+  }
+  if (d->d2s) {
+    IVF_CHECK_ARG(!has_mask, "conv3d: relu_mask unsupported with depth-to-space");
+    IVF_CHECK_ARG(d->bsT >= 1 && d->bsT <= 2 && d->bsH >= 1 && d->bsH <= 2 && d->bsW >= 1 && d->bsW <= 2,
+                  "conv3d: block strides must be 1 or 2");
+    IVF_CHECK_ARG(d->Cout % 8 == 0 && d->Cout <= 32, "conv3d: depth-to-space needs Cout = 8 * Cpad <= 32");
+    IVF_CHECK_ARG(d->dT > 0 && d->dH > 0 && d->dW > 0 && d->dC > 0 && d->dC <= d->Cout / 8,
+                  "conv3d: bad depth-to-space dims");
+    IVF_CHECK_ARG(d->out_coff + d->dC <= d->out_ld, "conv3d: d2s output window outside ld");
+  } else if (!d->out2) {
+    IVF_CHECK_ARG(d->out_coff + d->Cout <= d->out_ld, "conv3d: output window outside ld");
+  }
   return IVF_OK;
 }
 
-}  // namespace ivf
-
-using namespace ivf;
-
-extern "C" int ivf_conv3d(const ivf_conv3d_desc* d, const float* in, const float* w_packed,
-                          const float* scale, const float* shift, const float* relu_mask,
-                          float* out, ivf_stream_t stream) {
-  IVF_PROPAGATE(check_desc(d));
-  IVF_CHECK_ARG(in && w_packed && out, "conv3d: null pointer");
-  ConvKArgs a;
+// the kernels' view of a descriptor: the only place that copies its fields (the variant list passes no data pointers)
+static ConvKArgs fill_args(const ivf_conv3d_desc* d, const float* in, const float* w_packed, const float* scale,
+                           const float* shift, const float* relu_mask, float* out) {
+  ConvKArgs a{};
   a.in = in; a.w = w_packed; a.out = out; a.scale = scale; a.shift = shift; a.mask = relu_mask;
   a.B = d->B; a.Ti = d->Ti; a.Hi = d->Hi; a.Wi = d->Wi; a.Cin = d->Cin; a.in_ld = d->in_ld;
   a.in_coff = d->in_coff;
@@ -626,91 +661,96 @@ extern "C" int ivf_conv3d(const ivf_conv3d_desc* d, const float* in, const float
   a.K = d->kT * d->kH * d->kW * d->Cin;
   a.M = d->B * d->To * d->Ho * d->Wo;
   a.in2 = d->in2; a.in2_ld = d->in2_ld; a.in2_coff = d->in2_coff; a.K0 = d->K0;
-  if (d->in2) {
-    IVF_CHECK_ARG(d->kT * d->kH * d->kW == 1, "conv3d: a second input is only defined for 1x1x1 convs");
-    IVF_CHECK_ARG(d->K0 > 0 && d->K0 < d->Cin && d->K0 % 4 == 0 && d->in2_ld % 4 == 0 && d->in2_coff % 4 == 0 &&
-                      d->in2_coff + (d->Cin - d->K0) <= d->in2_ld,
-                  "conv3d: second-input channel window must be 4-aligned inside its row");
-  }
   a.out2 = d->out2; a.out2_ld = d->out2_ld; a.out2_coff = d->out2_coff; a.N0 = d->N0;
-  if (d->out2) {
-    IVF_CHECK_ARG(!d->accumulate && relu_mask == nullptr && !d->d2s,
-                  "conv3d: a second output window is a forward-epilogue feature (no accumulate / relu_mask / d2s)");
-    IVF_CHECK_ARG(d->N0 > 0 && d->N0 < d->Cout && d->out2_coff >= 0 && d->out2_coff + (d->Cout - d->N0) <= d->out2_ld &&
-                      d->out_coff + d->N0 <= d->out_ld,
-                  "conv3d: output windows [0,N0) / [N0,Cout) must fit their rows");
-    IVF_CHECK_ARG(d->variant == IVF_CONV_AUTO || (d->variant >= IVF_CONV_IGEMM_BASE && d->variant < IVF_CONV_PIX4),
-                  "conv3d: a second output window is served by the implicit-GEMM tiles only");
-  }
   a.gbo = d->gate_out; a.gbo2 = d->gate_out2; a.gbi = d->gate_in;
   a.gbo_ld = d->gate_out_ld; a.gbo_coff = d->gate_out_coff; a.gbo2_ld = d->gate_out2_ld;
   a.gbi_ld = d->gate_in_ld; a.gbi_coff = d->gate_in_coff;
-  if (d->gate_out || d->gate_out2 || d->gate_in) {
-    IVF_CHECK_ARG(!d->d2s && (d->Cout & 7) == 0 && (d->out_ld & 3) == 0 && (d->out_coff & 3) == 0,
-                  "conv3d: 1-bit gates need Cout %% 8 == 0 and 4-aligned output rows (the 16-byte epilogue)");
-    IVF_CHECK_ARG(d->variant != IVF_CONV_PIX4, "conv3d: the pix4 kernel does not record 1-bit gates");
-    IVF_CHECK_ARG(!d->out2 || ((d->N0 | d->out2_ld | d->out2_coff) & 3) == 0, "conv3d: 1-bit gates with out2 need 4-aligned windows");
-  }
-  if (d->gate_out || d->gate_out2) {
-    IVF_CHECK_ARG(!d->accumulate && relu_mask == nullptr && !d->gate_in,
-                  "conv3d: gate_out / gate_out2 are forward-epilogue records (no accumulate / relu_mask / gate_in)");
-    IVF_CHECK_ARG(!d->gate_out || ((d->gate_out_coff & 7) == 0 && d->gate_out_ld > 0), "conv3d: gate_out window must be 8-aligned");
-    IVF_CHECK_ARG(!d->gate_out2 || (d->out2 && (d->N0 & 7) == 0 && (d->out2_coff & 7) == 0 && d->gate_out2_ld > 0),
-                  "conv3d: gate_out2 needs out2 with 8-aligned N0 / out2_coff");
-  }
-  if (d->gate_in)
-    IVF_CHECK_ARG(relu_mask == nullptr && (d->gate_in_coff & 3) == 0 && d->gate_in_ld > 0,
-                  "conv3d: gate_in replaces relu_mask (give one of them) and needs a 4-aligned channel offset");
-  IVF_CHECK_ARG(d->math >= IVF_MATH_FP32 && d->math <= IVF_MATH_BF16ACT, "conv3d: math must be one of IVF_MATH_* (0..3)");
-  if (d->math == IVF_MATH_BF16ACT) {
-    // bf16 storage on both sides, except: the 4-channel-pixel strided conv reads fp32 pixels (pix4 kernel only), a
-    // depth-to-space backward writes fp32 (LDS-halo kernel only)
-    IVF_CHECK_ARG(!(d->d2s && (d->accumulate || d->relu)), "conv3d: bf16act depth-to-space output is a plain fp32 store");
-  }
   a.ldw = pack_ldw(a.K, d->math);
   a.wbf = reinterpret_cast<const unsigned short*>(w_packed);
   a.w_lo_off = (long)d->Cout * a.ldw;
   a.relu = d->relu; a.accumulate = d->accumulate; a.d2s = d->d2s;
   a.dT = d->dT; a.dH = d->dH; a.dW = d->dW; a.dC = d->dC;
   a.bsT = d->bsT; a.bsH = d->bsH; a.bsW = d->bsW;
-  if (d->d2s) {
-    IVF_CHECK_ARG(relu_mask == nullptr, "conv3d: relu_mask unsupported with depth-to-space");
-    IVF_CHECK_ARG(d->bsT >= 1 && d->bsT <= 2 && d->bsH >= 1 && d->bsH <= 2 && d->bsW >= 1 && d->bsW <= 2,
-                  "conv3d: block strides must be 1 or 2");
-    IVF_CHECK_ARG(d->Cout % 8 == 0 && d->Cout <= 32, "conv3d: depth-to-space needs Cout = 8 * Cpad <= 32");
-    IVF_CHECK_ARG(d->dT > 0 && d->dH > 0 && d->dW > 0 && d->dC > 0 && d->dC <= d->Cout / 8,
-                  "conv3d: bad depth-to-space dims");
-    IVF_CHECK_ARG(d->out_coff + d->dC <= d->out_ld, "conv3d: d2s output window outside ld");
-  } else if (!d->out2) {
-    IVF_CHECK_ARG(d->out_coff + d->Cout <= d->out_ld, "conv3d: output window outside ld");
-  }
-  if (d->math == 0) IVF_CHECK_ARG(a.ldw == a.K, "conv3d: internal ldw");
+  return a;
+}
+
+// bf16act: the two mixed-storage ends of the network have one kernel family each
+static bool act_stem(const ConvKArgs& a, const ivf_conv3d_desc* d) {   // fp32 pixels in: pix4 only
+  return d->math == IVF_MATH_BF16ACT && conv_pix4_supported(a);
+}
+static bool act_d2s(const ivf_conv3d_desc* d) { return d->math == IVF_MATH_BF16ACT && d->d2s; }   // fp32 out: LDS-halo only
+
+// Which kernel may serve a descriptor: the one statement of it.  ivf_conv3d asks it about the variant it is going to
+// launch, built-in or explicit, and ivf_conv3d_variants about every candidate it offers the tuner.  What depends on
+// more than the family -- the LDS a halo tile needs for this kernel size, a tile the arithmetic mode does not build,
+// the plain-GEMM form a second input needs -- is reported by the launch.
+struct Rule { int rc; const char* why; };
+#define IVF_RULE(cond, code, text) if (!(cond)) return Rule{code, text}
+static Rule variant_rule(const ConvKArgs& a, const ivf_conv3d_desc* d, int id) {
   const bool bf = d->math != IVF_MATH_FP32;
-  // bf16act: which kernels can serve the two mixed-storage ends of the network
-  const bool act_stem = d->math == IVF_MATH_BF16ACT && conv_pix4_supported(a);   // fp32 pixels in: pix4 only
-  const bool act_d2s = d->math == IVF_MATH_BF16ACT && d->d2s;                     // fp32 out: LDS-halo only
-  if (d->variant != IVF_CONV_AUTO) {
-    // explicit kernel variant (set by the plan's tuner)
-    if (d->variant == IVF_CONV_PIX4) {
-      IVF_CHECK_ARG(bf && conv_pix4_supported(a), "conv3d: pix4 variant needs a split-bf16 mode, 4-channel pixels, stride (1|2,2,2), k <= 7");
-      return conv_pix4_launch(a, d->math, IVF_CONV_PIX4, (hipStream_t)stream);
-    }
-    IVF_CHECK_ARG(!act_stem, "conv3d: bf16act reads fp32 pixels through the pix4 kernel only");
-    if (d->variant >= IVF_CONV_HALO_BASE) {
-      IVF_CHECK_ARG(bf && conv_halo_supported(a), "conv3d: halo variant needs a split-bf16 mode, stride 1, k in 2..4");
-      return conv_halo_launch_variant(a, d->math, d->variant - IVF_CONV_HALO_BASE, (hipStream_t)stream);
-    }
-    IVF_CHECK_ARG(!act_d2s, "conv3d: bf16act depth-to-space (fp32 output) is served by the LDS-halo kernel only");
-    return conv_igemm_launch_variant(a, d->math, d->variant - IVF_CONV_IGEMM_BASE, (hipStream_t)stream);
+  const int tile = id - IVF_CONV_IGEMM_BASE;
+  if (d->out2) {
+    IVF_RULE(tile >= 0 && id < IVF_CONV_PIX4, IVF_ERR_BAD_ARG, "conv3d: a second output window is served by the implicit-GEMM tiles only");
+  } else if (act_stem(a, d)) {
+    IVF_RULE(id == IVF_CONV_PIX4, IVF_ERR_BAD_ARG, "conv3d: bf16act reads fp32 pixels through the pix4 kernel only");
+    return Rule{IVF_OK, nullptr};   // (what else such a descriptor may ask of that kernel: resolve_variant)
   }
-  if (act_stem) {
-    IVF_CHECK_ARG(!d->out2 && !a.gbo, "conv3d: the pix4 kernel has no second output window / gate record");
-    return conv_pix4_launch(a, d->math, IVF_CONV_PIX4, (hipStream_t)stream);
+  if (id == IVF_CONV_PIX4) {
+    IVF_RULE(bf && conv_pix4_supported(a), IVF_ERR_BAD_ARG, "conv3d: pix4 variant needs a split-bf16 mode, 4-channel pixels, stride (1|2,2,2), k <= 7");
+    IVF_RULE(!a.gbo, IVF_ERR_BAD_ARG, "conv3d: the pix4 kernel does not record 1-bit gates");
+  } else if (id >= IVF_CONV_HALO_BASE) {
+    IVF_RULE(bf && conv_halo_supported(a), IVF_ERR_BAD_ARG, "conv3d: halo variant needs a split-bf16 mode, stride 1, k in 2..4");
+  } else {
+    IVF_RULE(!act_d2s(d), IVF_ERR_BAD_ARG, "conv3d: bf16act depth-to-space (fp32 output) is served by the LDS-halo kernel only");
+    IVF_RULE(tile >= 0 && tile < 8, IVF_ERR_BAD_ARG, "conv3d: unknown implicit-GEMM variant %d");
+    IVF_RULE(bf || !kIgemmTiles[tile].bf16_only, IVF_ERR_UNSUPPORTED, "conv3d: wide implicit-GEMM tiles exist for the split-bf16 modes only");
+    IVF_RULE(d->math != IVF_MATH_BF16X6 || kIgemmTiles[tile].fits_x6, IVF_ERR_UNSUPPORTED, "conv3d: this implicit-GEMM tile does not fit the LDS with three operand planes");
   }
-  if (bf && !d->out2 && conv_halo_supported(a)) return conv_halo_launch(a, d->math, (hipStream_t)stream);
-  IVF_CHECK_ARG(!act_d2s, "conv3d: bf16act depth-to-space needs the LDS-halo kernel (stride-1 form, k <= 4, Cin %% 8 == 0)");
-  if (bf && !d->out2 && !a.gbo && conv_pix4_supported(a)) return conv_pix4_launch(a, d->math, IVF_CONV_PIX4, (hipStream_t)stream);
-  return conv_launch(a, d->math, (hipStream_t)stream);
+  return Rule{IVF_OK, nullptr};
+}
+#undef IVF_RULE
+static bool variant_applicable(const ConvKArgs& a, const ivf_conv3d_desc* d, int id) { return variant_rule(a, d, id).rc == IVF_OK; }
+
+// the variant an untuned descriptor runs on, or a negative error
+static int default_variant(const ConvKArgs& a, const ivf_conv3d_desc* d) {
+  if (act_stem(a, d)) return IVF_CONV_PIX4;
+  if (variant_applicable(a, d, IVF_CONV_HALO_BASE)) return IVF_CONV_HALO_BASE + conv_halo_default(a, d->math);
+  IVF_CHECK_ARG(!act_d2s(d), "conv3d: bf16act depth-to-space needs the LDS-halo kernel (stride-1 form, k <= 4, Cin %% 8 == 0)");
+  if (variant_applicable(a, d, IVF_CONV_PIX4)) return IVF_CONV_PIX4;
+  return IVF_CONV_IGEMM_BASE + conv_igemm_default(a);
+}
+
+// the variant to launch for a request (IVF_CONV_AUTO or an id), or a negative error
+static int resolve_variant(const ConvKArgs& a, const ivf_conv3d_desc* d, int request) {
+  IVF_CHECK_ARG(!act_stem(a, d) || (!d->out2 && !a.gbo), "conv3d: the pix4 kernel has no second output window / gate record");
+  const int id = request == IVF_CONV_AUTO ? default_variant(a, d) : request;
+  if (request == IVF_CONV_AUTO && id < 0) return id;
+  const Rule r = variant_rule(a, d, id);
+  if (r.rc != IVF_OK) set_error(r.why, id);   // (one text names the id)
+  return r.rc != IVF_OK ? r.rc : id;
+}
+
+}  // namespace ivf
+
+using namespace ivf;
+
+extern "C" int ivf_conv3d(const ivf_conv3d_desc* d, const float* in, const float* w_packed,
+                          const float* scale, const float* shift, const float* relu_mask,
+                          float* out, ivf_stream_t stream) {
+  IVF_PROPAGATE(check_desc(d, relu_mask != nullptr));
+  IVF_CHECK_ARG(in && w_packed && out, "conv3d: null pointer");
+  ConvKArgs a = fill_args(d, in, w_packed, scale, shift, relu_mask, out);
+  const int id = resolve_variant(a, d, d->variant);
+  if (id < 0) return id;
+  hipStream_t s = (hipStream_t)stream;
+  if (id == IVF_CONV_PIX4) return conv_pix4_launch(a, d->math, s);
+  if (id >= IVF_CONV_HALO_BASE) return conv_halo_launch_variant(a, d->math, id - IVF_CONV_HALO_BASE, s);
+  return conv_igemm_launch_variant(a, d->math, id - IVF_CONV_IGEMM_BASE, s);
+}
+
+extern "C" int ivf_conv3d_default_variant(const ivf_conv3d_desc* d) {
+  IVF_PROPAGATE(check_desc(d, false));
+  return resolve_variant(fill_args(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), d, IVF_CONV_AUTO);
 }
 
 extern "C" int ivf_bn_fold(const float* gamma, const float* beta, const float* mean,
@@ -797,24 +837,17 @@ extern "C" size_t ivf_conv3d_pack_bwd_elems(int Cout, int CinPad, int kT, int kH
   return pack_floats((size_t)8 * CinPad, pack_ldw(KT * KH * KW * Cout, math), math);
 }
 
-// candidate kernel variants for a descriptor: fills ids[], returns the count
+// candidate kernel variants for a descriptor, in the order the tuner times them: fills ids[], returns the count
 extern "C" int ivf_conv3d_variants(const ivf_conv3d_desc* d, int* ids, int max_ids) {
   if (!d || !ids) return 0;
+  ConvKArgs a = fill_args(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  a.accumulate = 0;   // (a tuner lists once and launches both epilogue forms: a candidate that cannot accumulate says so then)
   int n = 0;
-  for (int v = 0; v < 3 && n < max_ids; ++v) ids[n++] = IVF_CONV_IGEMM_BASE + v;
-  const bool bf = d->math != IVF_MATH_FP32;
-  if (bf && d->kT * d->kH * d->kW == 1)
-    for (int v = (d->math == IVF_MATH_BF16X6 ? 6 : 3); v < 8 && n < max_ids; ++v) ids[n++] = IVF_CONV_IGEMM_BASE + v;
-  ConvKArgs a{};
-  a.sT = d->sT; a.sH = d->sH; a.sW = d->sW; a.kT = d->kT; a.kH = d->kH; a.kW = d->kW; a.Cin = d->Cin;
-  a.in_ld = d->in_ld; a.in_coff = d->in_coff; a.d2s = d->d2s; a.in2 = d->in2;
-  if (d->out2) return n;   // second output window: implicit-GEMM tiles only
-  // bf16act: the two mixed-storage ends of the network have one kernel family each
-  if (d->math == IVF_MATH_BF16ACT && conv_pix4_supported(a)) { ids[0] = IVF_CONV_PIX4; return 1; }
-  if (d->math == IVF_MATH_BF16ACT && d->d2s) n = 0;
-  if (bf && conv_halo_supported(a))
-    for (int v = 0; v < conv_halo_num_variants() && n < max_ids; ++v) ids[n++] = IVF_CONV_HALO_BASE + v;
-  if (bf && conv_pix4_supported(a) && !d->gate_out && n < max_ids) ids[n++] = IVF_CONV_PIX4;
+  auto offer = [&](int id) { if (n < max_ids && variant_applicable(a, d, id)) ids[n++] = id; };
+  const int tiles = d->kT * d->kH * d->kW == 1 ? 8 : 3;   // the wide and the small tiles are offered to 1x1x1 convs only
+  for (int v = 0; v < tiles; ++v) offer(IVF_CONV_IGEMM_BASE + v);
+  for (int v = 0; v < conv_halo_num_variants(); ++v) offer(IVF_CONV_HALO_BASE + v);
+  offer(IVF_CONV_PIX4);
   return n;
 }
 

@@ -1,5 +1,5 @@
 // LDS-halo convolution (conv3d_halo_impl.h): the AM_X3 instantiations (fp32 activations split hi/lo, 3 MFMA passes)
-// and the mode-independent host side: applicability, variant dispatch by arithmetic mode, built-in variant choice.
+// and the mode-independent host side: applicability, tile dispatch by arithmetic mode, built-in tile choice.
 #include "conv3d_halo_impl.h"
 
 namespace ivf {
@@ -28,35 +28,25 @@ int conv_halo_launch_variant(ConvKArgs& a, int math, int v, hipStream_t s) {
   return IVF_ERR_UNSUPPORTED;
 }
 
-// default choice when the plan has not been tuned
-int conv_halo_launch(ConvKArgs& a, int math, hipStream_t s) {
+// Built-in choice when the plan has not been tuned: tile index per output-channel width, for maps with 4-frame boxes
+// (To >= 4) and for shallower ones.
+struct HaloDefault { int width, deep, shallow; };
+static const HaloDefault kHaloDefault[5] = {{192, 0, 8}, {128, 1, 9}, {96, 3, 10}, {64, 5, 11}, {32, 7, 12}};
+// three activation planes: 16-channel chunks (4-frame boxes) or 2-frame boxes with at most 128 columns
+// (68 = the 8-wave form of tile 60: as fast or faster on data, and not at the register budget's edge)
+static const HaloDefault kHaloDefaultX6[5] = {{192, 68, 18}, {128, 61, 9}, {96, 20, 10}, {64, 21, 11}, {32, 37, 12}};
+
+int conv_halo_default(const ConvKArgs& a, int math) {
+  const HaloDefault* tab = math == IVF_MATH_BF16X6 ? kHaloDefaultX6 : kHaloDefault;
   // Output-channel tile width: every tile re-stages the halo, so weigh padded columns against
   // the number of tiles (a staging pass costs about as much as ~40 columns of MFMA work).
-  static const int widths[5] = {192, 128, 96, 64, 32};
-  int best = 32, best_cost = 1 << 30;
-  for (int w : widths) {
+  int best = 4, best_cost = 1 << 30;
+  for (int i = 0; i < 5; ++i) {
+    int w = tab[i].width;
     int cost = cdiv(a.Cout, w) * (w + 40);
-    if (cost < best_cost) { best_cost = cost; best = w; }
+    if (cost < best_cost) { best_cost = cost; best = i; }
   }
-  const bool deep = a.To >= 4;   // 4-frame boxes when the map has them, else 2-frame boxes
-  if (math == IVF_MATH_BF16X6) {
-    // three activation planes: 16-channel chunks (4-frame boxes) or 2-frame boxes with at most 128 columns
-    switch (best) {
-      // (68 = the 8-wave form of tile 60: as fast or faster on data, and not at the register budget's edge)
-      case 192: return conv_halo_launch_variant(a, math, deep ? 68 : 18, s);
-      case 128: return conv_halo_launch_variant(a, math, deep ? 61 : 9, s);
-      case 96: return conv_halo_launch_variant(a, math, deep ? 20 : 10, s);
-      case 64: return conv_halo_launch_variant(a, math, deep ? 21 : 11, s);
-      default: return conv_halo_launch_variant(a, math, deep ? 37 : 12, s);
-    }
-  }
-  switch (best) {
-    case 192: return conv_halo_launch_variant(a, math, deep ? 0 : 8, s);
-    case 128: return conv_halo_launch_variant(a, math, deep ? 1 : 9, s);
-    case 96: return conv_halo_launch_variant(a, math, deep ? 3 : 10, s);
-    case 64: return conv_halo_launch_variant(a, math, deep ? 5 : 11, s);
-    default: return conv_halo_launch_variant(a, math, deep ? 7 : 12, s);
-  }
+  return a.To >= 4 ? tab[best].deep : tab[best].shallow;
 }
 
 }  // namespace ivf

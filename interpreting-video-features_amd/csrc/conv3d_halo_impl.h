@@ -14,6 +14,7 @@
 #pragma once
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 
 #include "conv_common.h"
 
@@ -573,169 +574,155 @@ extern "C" int ivf_debug_halo_stamps(unsigned long long* out8, int reset) {
 namespace ivf {
 #endif
 
-template <int AM, int TT, int BN, int WROWS, int WCOLS, int KS = 1, int BKH = 32, int TH = 8, int TW = 8, int TPS = 1, bool DMA = false>
-static int launch_halo(ConvKArgs& a, int variant_id, hipStream_t s) {
-  constexpr int NPA = OpPlanes<AM>::A, NPB = OpPlanes<AM>::B;
-  constexpr int NT = (TT * TH * TW / WROWS) * (BN / WCOLS) * KS * 64;
-  constexpr int ROWB = (BKH + 8) * 2;
-  constexpr int ROWB_B = DMA ? BKH * 2 : ROWB;
-  const int HR = (TT + a.kT - 1) * halo_plane_rows<TT, TH, TW>(TH + a.kH - 1, TW + a.kW - 1);
-  size_t shm = (size_t)NPA * HR * ROWB + (size_t)2 * TPS * KS * NPB * BN * ROWB_B + (size_t)HR * sizeof(int);
-  // buffers that reuse the LDS from offset 0 once the tap loops are done (everything staged is dead by then): the
-  // tap-split reduction [BM][BN] floats, the depth-to-space tile [2 TT][16][16][4] floats
-  if (KS == 2) shm = std::max(shm, (size_t)TT * TH * TW * BN * 4);
-  if (a.d2s) shm = std::max(shm, (size_t)2 * TT * 256 * 4 * sizeof(float));
-  if (shm > 160 * 1024) {
-    set_error("conv3d_halo: %zu bytes of LDS needed", shm);
+// The tiles (ivf_conv3d_desc.variant = IVF_CONV_HALO_BASE + index): the kernel's template arguments after the operand
+// mode.  Box TT x TH x TW, BN output columns, wave tile WROWS x WCOLS, KS tap groups, BKH channels per chunk, TPS taps
+// per barrier, DMA weight stream.  Declared once: the launch table, the built set and the built-in choice
+// (conv3d_halo.hip) all read this array.
+struct HaloTile { int TT, BN, WROWS, WCOLS, KS, BKH, TH, TW, TPS; bool DMA; };
+constexpr HaloTile kHaloTiles[] = {
+    // 4- and 2-frame 8 x 8 boxes, 32-channel chunks, one tap per barrier
+    {4, 192, 32,  96, 1, 32, 8,  8, 1, false},   // 0
+    {4, 128, 64,  64, 1, 32, 8,  8, 1, false},
+    {4, 128, 32,  64, 1, 32, 8,  8, 1, false},
+    {4,  96, 32,  96, 1, 32, 8,  8, 1, false},
+    {4,  64, 32,  64, 1, 32, 8,  8, 1, false},
+    {4,  64, 64,  64, 2, 32, 8,  8, 1, false},   // 5
+    {4,  32, 32,  32, 1, 32, 8,  8, 1, false},
+    {4,  32, 64,  32, 2, 32, 8,  8, 1, false},
+    {2, 192, 32,  96, 1, 32, 8,  8, 1, false},
+    {2, 128, 32,  64, 1, 32, 8,  8, 1, false},
+    {2,  96, 32,  96, 1, 32, 8,  8, 1, false},   // 10
+    {2,  64, 32,  64, 1, 32, 8,  8, 1, false},
+    {2,  32, 32,  32, 1, 32, 8,  8, 1, false},
+    {2,  64, 64,  64, 2, 32, 8,  8, 1, false},
+    {2, 128, 64,  64, 1, 32, 8,  8, 1, false},
+    {4,  64, 32,  64, 2, 32, 8,  8, 1, false},   // 15
+    {4,  96, 32,  96, 2, 32, 8,  8, 1, false},
+    {4,  32, 32,  32, 2, 32, 8,  8, 1, false},
+    // 16-channel chunks (two workgroups per CU)
+    {2, 192, 32,  96, 1, 16, 8,  8, 1, false},   // 18
+    {2, 128, 32,  64, 1, 16, 8,  8, 1, false},
+    {4,  96, 32,  96, 1, 16, 8,  8, 1, false},   // 20
+    {4,  64, 32,  64, 1, 16, 8,  8, 1, false},
+    {2,  96, 32,  96, 1, 16, 8,  8, 1, false},
+    // 4 x 4 x 14 boxes (224 rows = 7 MFMA row tiles; exact on 28- and 14-wide maps)
+    {4, 192, 32,  96, 1, 32, 4, 14, 1, false},   // 23
+    {4, 128, 32,  64, 1, 32, 4, 14, 1, false},
+    {4,  96, 32,  96, 1, 32, 4, 14, 1, false},   // 25
+    {4,  64, 32,  64, 1, 32, 4, 14, 1, false},
+    {4,  32, 32,  32, 1, 32, 4, 14, 1, false},
+    {4,  64, 32,  32, 1, 32, 4, 14, 1, false},
+    {4,  32, 32,  32, 2, 32, 4, 14, 1, false},
+    {4, 128, 32, 128, 1, 32, 4, 14, 1, false},   // 30
+    // narrow outputs on 16-channel chunks (two or three workgroups per CU: one's per-tap barrier and LDS round trip
+    // hide under another's MFMAs -- what the 32-column stem backward-data is short of)
+    {2,  32, 64,  32, 2, 16, 8,  8, 1, false},   // 31
+    {2,  32, 32,  32, 2, 16, 8,  8, 1, false},
+    {2,  32, 32,  32, 1, 16, 8,  8, 1, false},
+    {2,  64, 32,  64, 2, 16, 8,  8, 1, false},
+    {2,  64, 64,  64, 2, 16, 8,  8, 1, false},   // 35
+    {4,  32, 64,  32, 2, 16, 8,  8, 1, false},
+    {4,  32, 32,  32, 2, 16, 8,  8, 1, false},
+    // several taps per barrier interval (narrow outputs; 16-channel chunks leave the LDS room; 46: k <= 3)
+    {4,  32, 32,  32, 2, 16, 8,  8, 4, false},   // 38
+    {4,  32, 64,  32, 2, 16, 8,  8, 4, false},
+    {4,  32, 32,  32, 2, 16, 8,  8, 2, false},   // 40
+    {2,  32, 32,  32, 2, 32, 8,  8, 2, false},
+    {4,  64, 32,  64, 1, 16, 8,  8, 2, false},
+    {4,  64, 32,  64, 1, 32, 8,  8, 2, false},
+    {4,  32, 32,  32, 1, 16, 8,  8, 4, false},
+    {4,  96, 32,  96, 1, 16, 8,  8, 2, false},   // 45
+    {4,  32, 32,  32, 2, 32, 8,  8, 2, false},
+    {4,  64, 32,  64, 1, 32, 4, 14, 2, false},
+    // 4 x 7 x 8 boxes (7 one-h-row tiles, conflict-free like the 4 x 8 x 8 ones; exact in H on 28- and 14-row maps)
+    {4, 192, 32,  96, 1, 32, 7,  8, 1, false},   // 48
+    {4, 128, 32,  64, 1, 32, 7,  8, 1, false},
+    {4,  96, 32,  96, 1, 16, 7,  8, 1, false},   // 50
+    {4,  64, 32,  64, 1, 16, 7,  8, 1, false},
+    // weight tiles by LDS-DMA (global_load_lds_dwordx4, swizzled 64-byte rows)
+    {4, 192, 32,  96, 1, 32, 8,  8, 1, true},    // 52
+    {4, 192, 32,  96, 1, 32, 4, 14, 1, true},
+    {4, 128, 32,  64, 1, 32, 4, 14, 1, true},
+    {4, 128, 32,  64, 1, 32, 8,  8, 1, true},    // 55
+    {4,  32, 32,  32, 2, 32, 8,  8, 1, true},
+    {4, 128, 32,  64, 1, 32, 7,  8, 1, true},
+    {4,  96, 32,  96, 1, 32, 8,  8, 1, true},
+    {4,  64, 32,  64, 1, 32, 8,  8, 1, true},
+    // wide tiles on 16-channel chunks (what fits beside the THREE activation planes of the 6-pass mode)
+    {4, 192, 32,  96, 1, 16, 8,  8, 1, false},   // 60
+    {4, 128, 32,  64, 1, 16, 8,  8, 1, false},
+    {4, 192, 32,  96, 1, 16, 4, 14, 1, false},
+    {4, 128, 32,  64, 1, 16, 4, 14, 1, false},
+    {4,  96, 32,  96, 1, 16, 4, 14, 1, false},
+    {4,  64, 32,  64, 1, 16, 4, 14, 1, false},   // 65
+    {4, 192, 32,  96, 1, 16, 7,  8, 1, false},
+    {4, 128, 32,  64, 1, 16, 7,  8, 1, false},
+    // the same wide tiles on 8 waves of 64-row wave tiles (two waves per SIMD with 256 registers each, 9 fragment
+    // reads per 12 MFMA groups instead of 12 per 9)
+    {4, 192, 64,  96, 1, 16, 8,  8, 1, false},   // 68
+    {4, 128, 64,  64, 1, 16, 8,  8, 1, false},
+};
+constexpr int HALO_NUM_VARIANTS = sizeof(kHaloTiles) / sizeof(kHaloTiles[0]);
+constexpr size_t HALO_LDS_MAX = 160 * 1024;
+
+// LDS bytes tile V needs with NPA activation and NPB weight planes: halo planes, two weight buffers, the row-offset
+// table; or, where larger, a buffer that reuses the LDS from offset 0 once the tap loops are done (everything staged is
+// dead by then): the tap-split reduction [BM][BN] floats, the depth-to-space tile [2 TT][16][16][4] floats.
+template <int V>
+constexpr size_t halo_lds_bytes(int NPA, int NPB, int kT, int kH, int kW, bool d2s) {
+  constexpr HaloTile t = kHaloTiles[V];
+  constexpr int ROWB = (t.BKH + 8) * 2, ROWB_B = t.DMA ? t.BKH * 2 : ROWB;
+  const size_t HR = (size_t)(t.TT + kT - 1) * halo_plane_rows<t.TT, t.TH, t.TW>(t.TH + kH - 1, t.TW + kW - 1);
+  size_t shm = NPA * HR * ROWB + (size_t)2 * t.TPS * t.KS * NPB * t.BN * ROWB_B + HR * sizeof(int);
+  if (t.KS == 2) shm = std::max(shm, (size_t)t.TT * t.TH * t.TW * t.BN * 4);
+  if (d2s) shm = std::max(shm, (size_t)2 * t.TT * 256 * 4 * sizeof(float));
+  return shm;
+}
+
+// A tile is built for an operand mode only if its LDS footprint fits for the 3x3x3 case (the 6-pass mode holds three
+// activation planes: mostly the 16-channel-chunk tiles remain); anything else reports IVF_ERR_UNSUPPORTED.
+template <int AM, int V>
+static int launch_halo(ConvKArgs& a, hipStream_t s) {
+  constexpr HaloTile t = kHaloTiles[V];
+  if constexpr (halo_lds_bytes<V>(OpPlanes<AM>::A, OpPlanes<AM>::B, 3, 3, 3, false) > HALO_LDS_MAX) {
+    set_error("conv3d_halo: variant %d needs more than 160 KB of LDS in this arithmetic mode", V);
     return IVF_ERR_UNSUPPORTED;
-  }
-  static LdsAttrOnce once;
-  IVF_PROPAGATE(raise_lds_limit(reinterpret_cast<const void*>(&conv3d_halo_kernel<AM, TT, BN, WROWS, WCOLS, KS, BKH, TH, TW, TPS, DMA>), 160 * 1024, once));
-  const int tilesT = cdiv(a.To, TT), tilesH = cdiv(a.Ho, TH), tilesW = cdiv(a.Wo, TW);
-  a.ntiles = cdiv(a.Cout, BN);
-  a.mtiles = a.B * tilesT * tilesH * tilesW;
-  dim3 grid(a.mtiles * a.ntiles);
-  prof_name(IVF_CONV_HALO_BASE + variant_id, "conv3d_halo_kernel<%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%s>", AM, TT, BN, WROWS, WCOLS, KS,
-            BKH, TH, TW, TPS, DMA ? "true" : "false");
-  const bool timed = prof_begin(s, IVF_CONV_HALO_BASE + variant_id);
-  hipLaunchKernelGGL((conv3d_halo_kernel<AM, TT, BN, WROWS, WCOLS, KS, BKH, TH, TW, TPS, DMA>), grid, dim3(NT), shm, s, a, tilesT, tilesH, tilesW);
-  if (timed) prof_end(s);
-  IVF_CHECK_LAUNCH();
-  return IVF_OK;
-}
-
-
-// Variant table (ivf_conv3d_desc.variant = IVF_CONV_HALO_BASE + index).
-//            TT  BN  wave rows x cols  tap groups
-//  0: 4 192  32 x 96  1      1: 4 128  64 x 64  1     2: 4 128  32 x 64  1     3: 4  96  32 x 96  1
-//  4: 4  64  32 x 64  1      5: 4  64  64 x 64  2     6: 4  32  32 x 32  1     7: 4  32  64 x 32  2
-//  8: 2 192  32 x 96  1      9: 2 128  32 x 64  1    10: 2  96  32 x 96  1    11: 2  64  32 x 64  1
-// 12: 2  32  32 x 32  1     13: 2  64  64 x 64  2    14: 2 128  64 x 64  1
-// 15: 4  64  32 x 64  2     16: 4  96  32 x 96  2    17: 4  32  32 x 32  2
-// 16-channel chunks (two workgroups per CU):
-// 18: 2 192  32 x 96  1     19: 2 128  32 x 64  1    20: 4  96  32 x 96  1    21: 4  64  32 x 64  1
-// 22: 2  96  32 x 96  1
-// 4 x 4 x 14 boxes (224 rows = 7 MFMA row tiles; exact on 28- and 14-wide maps):
-// 23: 192  32 x 96  1     24: 128  32 x 64  1     25:  96  32 x 96  1     26:  64  32 x 64  1
-// 27:  32  32 x 32  1     28:  64  32 x 32  1     29:  32  32 x 32  2     30: 128  32 x 128 1
-// narrow outputs, 2-frame boxes with 16-channel chunks (two or three workgroups per CU: one's per-tap barrier
-// and LDS round trip hide under another's MFMAs -- what the 32-column stem backward-data is short of):
-// 31: 2 32 64 x 32 2    32: 2 32 32 x 32 2    33: 2 32 32 x 32 1    34: 2 64 32 x 64 2    35: 2 64 64 x 64 2
-// 36: 4 32 64 x 32 2 (16)   37: 4 32 32 x 32 2 (16)
-// several taps per barrier interval (narrow outputs; 16-channel chunks leave the LDS room):
-// 38: 4 32 32 x 32 2 (16) x4 taps   39: 4 32 64 x 32 2 (16) x4   40: 4 32 32 x 32 2 (16) x2   41: 2 32 32 x 32 2 (32) x2
-// 42: 4 64 32 x 64 1 (16) x2        43: 4 64 32 x 64 1 (32) x2   44: 4 32 32 x 32 1 (16) x4   45: 4 96 32 x 96 1 (16) x2
-// 46: 4 32 32 x 32 2 (32) x2 (k <= 3)   47: 4x4x14 box, 64 32 x 64 1 (32) x2
-// 4 x 7 x 8 boxes (7 one-h-row tiles, conflict-free like the 4 x 8 x 8 ones; exact in H on 28- and 14-row maps):
-// 48: 192 32 x 96 1 (32)   49: 128 32 x 64 1 (32)   50: 96 32 x 96 1 (16)   51: 64 32 x 64 1 (16)
-// weight tiles by LDS-DMA (global_load_lds_dwordx4, swizzled 64-byte rows):
-// 52: 4 192 32 x 96 1 (32) 8x8   53: same, 4x14   54: 4 128 32 x 64 1 (32) 4x14   55: 4 128 32 x 64 1 (32) 8x8
-// 56: 4 32 32 x 32 2 (32) 8x8    57: 4 128 32 x 64 1 (32) 7x8   58: 4 96 32 x 96 1 (32) 8x8   59: 4 64 32 x 64 1 (32) 8x8
-// wide tiles on 16-channel chunks (what fits beside the THREE activation planes of the 6-pass mode):
-// 60: 4 192 32 x 96 1 (16) 8x8   61: 4 128 32 x 64 1 (16) 8x8   62: 4 192 32 x 96 1 (16) 4x14   63: 4 128 32 x 64 1 (16) 4x14
-// 64: 4 96 32 x 96 1 (16) 4x14   65: 4 64 32 x 64 1 (16) 4x14    66: 4 192 32 x 96 1 (16) 7x8    67: 4 128 32 x 64 1 (16) 7x8
-// the same wide tiles on 8 waves of 64-row wave tiles (two waves per SIMD with 256 registers each, 9 fragment reads per
-// 12 MFMA groups instead of 12 per 9):
-// 68: 4 192 64 x 96 1 (16) 8x8   69: 4 128 64 x 64 1 (16) 8x8
-constexpr int HALO_NUM_VARIANTS = 70;
-
-// A variant is built for an operand mode only if its LDS footprint fits for the 3x3x3 case (the 6-pass mode holds
-// three activation planes: mostly the 16-channel-chunk variants remain); anything else reports IVF_ERR_UNSUPPORTED.
-template <int AM, int TT, int BN, int KS, int BKH, int TH, int TW, int TPS, bool DMA>
-constexpr bool halo_variant_built() {
-  constexpr int ROWB = (BKH + 8) * 2, ROWB_B = DMA ? BKH * 2 : ROWB;
-  constexpr int HH = TH + 2, HW = TW + 2;
-  constexpr int PS = HH * HW + ((TT == 4 && TW == 8) ? (4 - (HH * HW) % 8 + 8) % 8 : 0);
-  constexpr long HR = (long)(TT + 2) * PS;
-  constexpr long shm = OpPlanes<AM>::A * HR * ROWB + 2L * TPS * KS * OpPlanes<AM>::B * BN * ROWB_B + HR * 4;
-  return shm <= 160 * 1024;
-}
-template <int AM, int TT, int BN, int WROWS, int WCOLS, int KS = 1, int BKH = 32, int TH = 8, int TW = 8, int TPS = 1, bool DMA = false>
-static int launch_halo_if(ConvKArgs& a, int variant_id, hipStream_t s) {
-  if constexpr (halo_variant_built<AM, TT, BN, KS, BKH, TH, TW, TPS, DMA>()) {
-    return launch_halo<AM, TT, BN, WROWS, WCOLS, KS, BKH, TH, TW, TPS, DMA>(a, variant_id, s);
   } else {
-    set_error("conv3d_halo: variant %d needs more than 160 KB of LDS in this arithmetic mode", variant_id);
-    return IVF_ERR_UNSUPPORTED;
+    constexpr auto kernel = &conv3d_halo_kernel<AM, t.TT, t.BN, t.WROWS, t.WCOLS, t.KS, t.BKH, t.TH, t.TW, t.TPS, t.DMA>;
+    constexpr int NT = (t.TT * t.TH * t.TW / t.WROWS) * (t.BN / t.WCOLS) * t.KS * 64;
+    const size_t shm = halo_lds_bytes<V>(OpPlanes<AM>::A, OpPlanes<AM>::B, a.kT, a.kH, a.kW, a.d2s);
+    if (shm > HALO_LDS_MAX) {
+      set_error("conv3d_halo: %zu bytes of LDS needed", shm);
+      return IVF_ERR_UNSUPPORTED;
+    }
+    static LdsAttrOnce once;
+    IVF_PROPAGATE(raise_lds_limit(reinterpret_cast<const void*>(kernel), HALO_LDS_MAX, once));
+    const int tilesT = cdiv(a.To, t.TT), tilesH = cdiv(a.Ho, t.TH), tilesW = cdiv(a.Wo, t.TW);
+    a.ntiles = cdiv(a.Cout, t.BN);
+    a.mtiles = a.B * tilesT * tilesH * tilesW;
+    prof_name(IVF_CONV_HALO_BASE + V, "conv3d_halo_kernel<%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%s>", AM, t.TT, t.BN, t.WROWS, t.WCOLS,
+              t.KS, t.BKH, t.TH, t.TW, t.TPS, t.DMA ? "true" : "false");
+    const bool timed = prof_begin(s, IVF_CONV_HALO_BASE + V);
+    hipLaunchKernelGGL(kernel, dim3(a.mtiles * a.ntiles), dim3(NT), shm, s, a, tilesT, tilesH, tilesW);
+    if (timed) prof_end(s);
+    IVF_CHECK_LAUNCH();
+    return IVF_OK;
   }
+}
+
+template <int AM, size_t... V>
+static int halo_dispatch(ConvKArgs& a, int v, hipStream_t s, std::index_sequence<V...>) {
+  static constexpr int (*launch[])(ConvKArgs&, hipStream_t) = {&launch_halo<AM, (int)V>...};
+  return launch[v](a, s);
 }
 
 template <int AM>
 int conv_halo_launch_variant_am(ConvKArgs& a, int v, hipStream_t s) {
-  switch (v) {
-    case 0: return launch_halo_if<AM, 4, 192, 32, 96>(a, 0, s);
-    case 1: return launch_halo_if<AM, 4, 128, 64, 64>(a, 1, s);
-    case 2: return launch_halo_if<AM, 4, 128, 32, 64>(a, 2, s);
-    case 3: return launch_halo_if<AM, 4, 96, 32, 96>(a, 3, s);
-    case 4: return launch_halo_if<AM, 4, 64, 32, 64>(a, 4, s);
-    case 5: return launch_halo_if<AM, 4, 64, 64, 64, 2>(a, 5, s);
-    case 6: return launch_halo_if<AM, 4, 32, 32, 32>(a, 6, s);
-    case 7: return launch_halo_if<AM, 4, 32, 64, 32, 2>(a, 7, s);
-    case 8: return launch_halo_if<AM, 2, 192, 32, 96>(a, 8, s);
-    case 9: return launch_halo_if<AM, 2, 128, 32, 64>(a, 9, s);
-    case 10: return launch_halo_if<AM, 2, 96, 32, 96>(a, 10, s);
-    case 11: return launch_halo_if<AM, 2, 64, 32, 64>(a, 11, s);
-    case 12: return launch_halo_if<AM, 2, 32, 32, 32>(a, 12, s);
-    case 13: return launch_halo_if<AM, 2, 64, 64, 64, 2>(a, 13, s);
-    case 14: return launch_halo_if<AM, 2, 128, 64, 64>(a, 14, s);
-    case 15: return launch_halo_if<AM, 4, 64, 32, 64, 2>(a, 15, s);
-    case 16: return launch_halo_if<AM, 4, 96, 32, 96, 2>(a, 16, s);
-    case 17: return launch_halo_if<AM, 4, 32, 32, 32, 2>(a, 17, s);
-    case 18: return launch_halo_if<AM, 2, 192, 32, 96, 1, 16>(a, 18, s);
-    case 19: return launch_halo_if<AM, 2, 128, 32, 64, 1, 16>(a, 19, s);
-    case 20: return launch_halo_if<AM, 4, 96, 32, 96, 1, 16>(a, 20, s);
-    case 21: return launch_halo_if<AM, 4, 64, 32, 64, 1, 16>(a, 21, s);
-    case 22: return launch_halo_if<AM, 2, 96, 32, 96, 1, 16>(a, 22, s);
-    case 23: return launch_halo_if<AM, 4, 192, 32, 96, 1, 32, 4, 14>(a, 23, s);
-    case 24: return launch_halo_if<AM, 4, 128, 32, 64, 1, 32, 4, 14>(a, 24, s);
-    case 25: return launch_halo_if<AM, 4, 96, 32, 96, 1, 32, 4, 14>(a, 25, s);
-    case 26: return launch_halo_if<AM, 4, 64, 32, 64, 1, 32, 4, 14>(a, 26, s);
-    case 27: return launch_halo_if<AM, 4, 32, 32, 32, 1, 32, 4, 14>(a, 27, s);
-    case 28: return launch_halo_if<AM, 4, 64, 32, 32, 1, 32, 4, 14>(a, 28, s);
-    case 29: return launch_halo_if<AM, 4, 32, 32, 32, 2, 32, 4, 14>(a, 29, s);
-    case 30: return launch_halo_if<AM, 4, 128, 32, 128, 1, 32, 4, 14>(a, 30, s);
-    case 31: return launch_halo_if<AM, 2, 32, 64, 32, 2, 16>(a, 31, s);
-    case 32: return launch_halo_if<AM, 2, 32, 32, 32, 2, 16>(a, 32, s);
-    case 33: return launch_halo_if<AM, 2, 32, 32, 32, 1, 16>(a, 33, s);
-    case 34: return launch_halo_if<AM, 2, 64, 32, 64, 2, 16>(a, 34, s);
-    case 35: return launch_halo_if<AM, 2, 64, 64, 64, 2, 16>(a, 35, s);
-    case 36: return launch_halo_if<AM, 4, 32, 64, 32, 2, 16>(a, 36, s);
-    case 37: return launch_halo_if<AM, 4, 32, 32, 32, 2, 16>(a, 37, s);
-    case 38: return launch_halo_if<AM, 4, 32, 32, 32, 2, 16, 8, 8, 4>(a, 38, s);
-    case 39: return launch_halo_if<AM, 4, 32, 64, 32, 2, 16, 8, 8, 4>(a, 39, s);
-    case 40: return launch_halo_if<AM, 4, 32, 32, 32, 2, 16, 8, 8, 2>(a, 40, s);
-    case 41: return launch_halo_if<AM, 2, 32, 32, 32, 2, 32, 8, 8, 2>(a, 41, s);
-    case 42: return launch_halo_if<AM, 4, 64, 32, 64, 1, 16, 8, 8, 2>(a, 42, s);
-    case 43: return launch_halo_if<AM, 4, 64, 32, 64, 1, 32, 8, 8, 2>(a, 43, s);
-    case 44: return launch_halo_if<AM, 4, 32, 32, 32, 1, 16, 8, 8, 4>(a, 44, s);
-    case 45: return launch_halo_if<AM, 4, 96, 32, 96, 1, 16, 8, 8, 2>(a, 45, s);
-    case 46: return launch_halo_if<AM, 4, 32, 32, 32, 2, 32, 8, 8, 2>(a, 46, s);
-    case 47: return launch_halo_if<AM, 4, 64, 32, 64, 1, 32, 4, 14, 2>(a, 47, s);
-    case 48: return launch_halo_if<AM, 4, 192, 32, 96, 1, 32, 7, 8>(a, 48, s);
-    case 49: return launch_halo_if<AM, 4, 128, 32, 64, 1, 32, 7, 8>(a, 49, s);
-    case 50: return launch_halo_if<AM, 4, 96, 32, 96, 1, 16, 7, 8>(a, 50, s);
-    case 51: return launch_halo_if<AM, 4, 64, 32, 64, 1, 16, 7, 8>(a, 51, s);
-    case 52: return launch_halo_if<AM, 4, 192, 32, 96, 1, 32, 8, 8, 1, true>(a, 52, s);
-    case 53: return launch_halo_if<AM, 4, 192, 32, 96, 1, 32, 4, 14, 1, true>(a, 53, s);
-    case 54: return launch_halo_if<AM, 4, 128, 32, 64, 1, 32, 4, 14, 1, true>(a, 54, s);
-    case 55: return launch_halo_if<AM, 4, 128, 32, 64, 1, 32, 8, 8, 1, true>(a, 55, s);
-    case 56: return launch_halo_if<AM, 4, 32, 32, 32, 2, 32, 8, 8, 1, true>(a, 56, s);
-    case 57: return launch_halo_if<AM, 4, 128, 32, 64, 1, 32, 7, 8, 1, true>(a, 57, s);
-    case 58: return launch_halo_if<AM, 4, 96, 32, 96, 1, 32, 8, 8, 1, true>(a, 58, s);
-    case 59: return launch_halo_if<AM, 4, 64, 32, 64, 1, 32, 8, 8, 1, true>(a, 59, s);
-    case 60: return launch_halo_if<AM, 4, 192, 32, 96, 1, 16>(a, 60, s);
-    case 61: return launch_halo_if<AM, 4, 128, 32, 64, 1, 16>(a, 61, s);
-    case 62: return launch_halo_if<AM, 4, 192, 32, 96, 1, 16, 4, 14>(a, 62, s);
-    case 63: return launch_halo_if<AM, 4, 128, 32, 64, 1, 16, 4, 14>(a, 63, s);
-    case 64: return launch_halo_if<AM, 4, 96, 32, 96, 1, 16, 4, 14>(a, 64, s);
-    case 65: return launch_halo_if<AM, 4, 64, 32, 64, 1, 16, 4, 14>(a, 65, s);
-    case 66: return launch_halo_if<AM, 4, 192, 32, 96, 1, 16, 7, 8>(a, 66, s);
-    case 67: return launch_halo_if<AM, 4, 128, 32, 64, 1, 16, 7, 8>(a, 67, s);
-    case 68: return launch_halo_if<AM, 4, 192, 64, 96, 1, 16>(a, 68, s);
-    case 69: return launch_halo_if<AM, 4, 128, 64, 64, 1, 16>(a, 69, s);
+  if (v < 0 || v >= HALO_NUM_VARIANTS) {
+    set_error("conv3d_halo: unknown variant %d", v);
+    return IVF_ERR_BAD_ARG;
   }
-  set_error("conv3d_halo: unknown variant %d", v);
-  return IVF_ERR_BAD_ARG;
+  return halo_dispatch<AM>(a, v, s, std::make_index_sequence<HALO_NUM_VARIANTS>{});
 }
 
 }  // namespace ivf

@@ -313,7 +313,7 @@ int conv_pix4_supported(const ConvKArgs& a) {
 }
 
 template <int AM, int P4_TT, bool OB>
-static int launch_pix4(ConvKArgs& a, int variant_id, hipStream_t s) {
+static int launch_pix4(ConvKArgs& a, hipStream_t s) {
   constexpr int NPA = OpPlanes<AM>::A, NPB = OpPlanes<AM>::B;
   const int HT = (P4_TT - 1) * a.sT + a.kT, HH = 2 * (P4_TH - 1) + a.kH;
   const size_t shm = (size_t)NPA * HT * HH * P4_PW * 8 + (size_t)3 * NPB * P4_BN * P4_ROWB;
@@ -326,8 +326,8 @@ static int launch_pix4(ConvKArgs& a, int variant_id, hipStream_t s) {
   const int tilesT = cdiv(a.To, P4_TT), tilesH = cdiv(a.Ho, P4_TH), tilesW = cdiv(a.Wo, P4_TW);
   a.ntiles = cdiv(a.Cout, P4_BN);
   a.mtiles = a.B * tilesT * tilesH * tilesW;
-  prof_name(variant_id, "conv3d_pix4_kernel<%d,%d,%s>", AM, P4_TT, OB ? "true" : "false");
-  const bool timed = prof_begin(s, variant_id);
+  prof_name(IVF_CONV_PIX4, "conv3d_pix4_kernel<%d,%d,%s>", AM, P4_TT, OB ? "true" : "false");
+  const bool timed = prof_begin(s, IVF_CONV_PIX4);
   static int cus = 0;
   if (!cus) {
     int dev = 0;
@@ -342,11 +342,12 @@ static int launch_pix4(ConvKArgs& a, int variant_id, hipStream_t s) {
   return IVF_OK;
 }
 
-int conv_pix4_launch(ConvKArgs& a, int math, int variant_id, hipStream_t s) {
+int conv_pix4_launch(ConvKArgs& a, int math, hipStream_t s) {
+  IVF_CHECK_ARG(!a.gbo && !a.gbo2 && !a.gbi, "conv3d: the pix4 kernel does not record 1-bit gates");
   switch (math) {
-    case IVF_MATH_BF16X3: return launch_pix4<AM_X3, 4, false>(a, variant_id, s);
-    case IVF_MATH_BF16ACT: return launch_pix4<AM_X3, 4, true>(a, variant_id, s);    // fp32 pixels in, bf16 out
-    case IVF_MATH_BF16X6: return launch_pix4<AM_X6, 2, false>(a, variant_id, s);   // 2-frame boxes: three pixel images in LDS
+    case IVF_MATH_BF16X3: return launch_pix4<AM_X3, 4, false>(a, s);
+    case IVF_MATH_BF16ACT: return launch_pix4<AM_X3, 4, true>(a, s);    // fp32 pixels in, bf16 out
+    case IVF_MATH_BF16X6: return launch_pix4<AM_X6, 2, false>(a, s);   // 2-frame boxes: three pixel images in LDS
   }
   set_error("conv3d_pix4: arithmetic mode %d has no pix4 kernel", math);
   return IVF_ERR_UNSUPPORTED;

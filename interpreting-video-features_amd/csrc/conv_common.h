@@ -410,14 +410,13 @@ __device__ __forceinline__ void conv_epilogue(const ConvKArgs& a, f32x16 (&acc)[
   }
 }
 
-int conv_launch(ConvKArgs& a, int math, hipStream_t s);
 int conv_igemm_launch_variant(ConvKArgs& a, int math, int v, hipStream_t s);
 int conv_halo_supported(const ConvKArgs& a);
-int conv_halo_launch(ConvKArgs& a, int math, hipStream_t s);
+int conv_halo_default(const ConvKArgs& a, int math);   // built-in tile of an untuned descriptor
 int conv_halo_num_variants();
 int conv_halo_launch_variant(ConvKArgs& a, int math, int v, hipStream_t s);
 int conv_pix4_supported(const ConvKArgs& a);
-int conv_pix4_launch(ConvKArgs& a, int math, int variant_id, hipStream_t s);
+int conv_pix4_launch(ConvKArgs& a, int math, hipStream_t s);
 // bf16 planes of a weight pack in an arithmetic mode (0: fp32 pack)
 static inline int math_planes(int math) { return math == IVF_MATH_BF16X6 ? 3 : (math == IVF_MATH_FP32 ? 0 : 2); }
 

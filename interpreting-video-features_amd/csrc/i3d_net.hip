@@ -395,7 +395,6 @@ static void fill_conv_fwd(const ivf_i3d* n, const Op& o, int b, ivf_conv3d_desc*
   d->pT = o.p[0]; d->pH = o.p[1]; d->pW = o.p[2];
   d->relu = 1;
   d->math = n->cfg.math;
-  d->variant = o.var_fwd;
   if (o.dst2 >= 0) {   // the fused [b0 | b1a | b2a] GEMM: o.cout spans the three units
     d->N0 = o.n0;
     d->out2 = n->act(o.dst2);
@@ -425,7 +424,6 @@ static void fill_conv_bwd(const ivf_i3d* n, const Op& o, int b, ivf_conv3d_desc*
   d->accumulate = o.bwd_accumulate;
   d->mask_ld = s.C; d->mask_coff = o.src_coff;
   d->math = n->cfg.math;
-  d->variant = o.var_bwd;
   if (o.bwd_fused) {
     // one GEMM over [dY_b0 | dT_b1a | dT_b2a] -> d(input of the module)
     const ActBuf& t12 = n->bufs[o.src2];
@@ -463,6 +461,35 @@ static void fill_pool(const ivf_i3d* n, const Op& o, int b, ivf_pool3d_desc* d) 
   // OUTPUT, before its own ReLU gate, so the true arg-max must be kept even in dead windows)
   d->gate_nonpos = o.bwd_mask && o.src != n->cam_buf;
   d->act_bf16 = n->act16();
+}
+
+// One convolution site -- an op in one direction (0 forward, 1 backward-data) -- on b clips with kernel variant
+// `variant`.  Forward reads the unit's own pack or the fused [b0 | b1a | b2a] group's; backward the unit's own or the
+// fused 1x1x1 GEMM's, and gates the gradient it writes through the 1-bit record where the plan keeps one, else through
+// the fp32 activation (not at all for the Grad-CAM target: see fill_pool).
+static int launch_conv_site(const ivf_i3d* n, const Op& o, int dir, int b, int variant, hipStream_t s) {
+  const ConvLayer& L = n->convs[o.conv];
+  const float* W = n->warena;
+  ivf_conv3d_desc d;
+  if (dir == 0) {
+    fill_conv_fwd(n, o, b, &d);
+    d.variant = variant;
+    prof_set_flops(o.flops_per_clip * b);
+    const size_t wf = o.fwd_group ? L.grp_wf_off : L.wf_off, sc = o.fwd_group ? L.grp_scale_off : L.scale_off,
+                 sh = o.fwd_group ? L.grp_shift_off : L.shift_off;
+    return ivf_conv3d(&d, n->act(o.src), W + wf, W + sc, W + sh, nullptr, n->act(o.dst), s);
+  }
+  fill_conv_bwd(n, o, b, &d);
+  d.variant = variant;
+  const float* gate = (o.bwd_mask && o.src != n->cam_buf) ? n->act(o.src) : nullptr;
+  if (gate && n->bufs[o.src].need_gate) {
+    d.gate_in = n->gatebits(o.src);
+    d.gate_in_ld = n->bufs[o.src].C / 8;
+    d.gate_in_coff = o.src_coff;
+    gate = nullptr;
+  }
+  prof_set_flops((o.bwd_fused ? o.flops_bwd_per_clip : o.flops_per_clip) * b);
+  return ivf_conv3d(&d, n->grad(o.dst), W + (o.bwd_fused ? L.fus_wb_off : L.wb_off), nullptr, nullptr, gate, n->grad(o.src), s);
 }
 
 static int check_ready(const ivf_i3d* n, int b) {
@@ -529,17 +556,7 @@ static int run_forward(ivf_i3d* n, int b, float* logits, float* probs, hipStream
     hipStream_t st = o.side_fwd ? lane.side() : s;
     prof_set_site(o.type == Op::CONV ? 2 * (int)(&o - n->ops.data()) : -1);
     if (o.type == Op::CONV) {
-      const ConvLayer& L = n->convs[o.conv];
-      ivf_conv3d_desc d;
-      fill_conv_fwd(n, o, b, &d);
-      prof_set_flops(o.flops_per_clip * b);
-      int rc;
-      if (o.fwd_group)
-        rc = ivf_conv3d(&d, n->act(o.src), n->warena + L.grp_wf_off, n->warena + L.grp_scale_off,
-                        n->warena + L.grp_shift_off, nullptr, n->act(o.dst), st);
-      else
-        rc = ivf_conv3d(&d, n->act(o.src), n->warena + L.wf_off, n->warena + L.scale_off, n->warena + L.shift_off,
-                        nullptr, n->act(o.dst), st);
+      int rc = launch_conv_site(n, o, 0, b, o.var_fwd, st);
       if (rc != IVF_OK) { lane.join(); return rc; }
     } else {
       ivf_pool3d_desc d;
@@ -585,28 +602,16 @@ static int run_backward(ivf_i3d* n, int b, const int* target, const float* dout,
     // the fused 1x1x1 backward GEMM accumulates into grad(input) after the pool's backward has written it
     if (o.bwd_fused) lane.join();
     hipStream_t st = o.side_bwd ? lane.side() : s;
-    const float* gate = (o.bwd_mask && o.src != n->cam_buf) ? n->act(o.src) : nullptr;
     prof_set_site(o.type == Op::CONV ? 2 * i + 1 : -1);
     int rc;
     if (o.type == Op::CONV) {
-      const ConvLayer& L = n->convs[o.conv];
-      ivf_conv3d_desc d;
-      fill_conv_bwd(n, o, b, &d);
-      const float* fgate = gate;
-      if (gate && n->bufs[o.src].need_gate) {   // the 1-bit record instead of the fp32 activation
-        d.gate_in = n->gatebits(o.src);
-        d.gate_in_ld = n->bufs[o.src].C / 8;
-        d.gate_in_coff = o.src_coff;
-        fgate = nullptr;
-      }
-      prof_set_flops((o.bwd_fused ? o.flops_bwd_per_clip : o.flops_per_clip) * b);
-      rc = ivf_conv3d(&d, n->grad(o.dst), n->warena + (o.bwd_fused ? L.fus_wb_off : L.wb_off), nullptr, nullptr, fgate,
-                      n->grad(o.src), st);
+      rc = launch_conv_site(n, o, 1, b, o.var_bwd, st);
     } else {
       ivf_pool3d_desc d;
       fill_pool(n, o, b, &d);
       // sole writer of a ReLU output's gradient: gated through the arg-max record (fill_pool);
       // with other writers before it the accumulated sum still needs the explicit gate
+      const float* gate = (o.bwd_mask && o.src != n->cam_buf) ? n->act(o.src) : nullptr;
       rc = ivf_maxpool3d_bwd(&d, n->grad(o.dst), n->at<unsigned char>(o.idx_off), n->grad(o.src),
                              o.bwd_accumulate ? gate : nullptr, o.bwd_accumulate, st);
     }
@@ -984,23 +989,7 @@ extern "C" int ivf_i3d_autotune(ivf_i3d_t* net, int b, int reps, ivf_stream_t st
       float best = 1e30f;
       int best_id = IVF_CONV_AUTO;
       for (int k = 0; k < nv; ++k) {
-        d.variant = ids[k];
-        auto run = [&]() {
-          if (dir == 0)
-            return o.fwd_group ? ivf_conv3d(&d, net->act(o.src), net->warena + L.grp_wf_off,
-                                            net->warena + L.grp_scale_off, net->warena + L.grp_shift_off, nullptr,
-                                            net->act(o.dst), s)
-                               : ivf_conv3d(&d, net->act(o.src), net->warena + L.wf_off, net->warena + L.scale_off,
-                                            net->warena + L.shift_off, nullptr, net->act(o.dst), s);
-          const bool bits = o.bwd_mask && net->bufs[o.src].need_gate;
-          if (bits) {
-            d.gate_in = net->gatebits(o.src);
-            d.gate_in_ld = net->bufs[o.src].C / 8;
-            d.gate_in_coff = o.src_coff;
-          }
-          return ivf_conv3d(&d, net->grad(o.dst), net->warena + (o.bwd_fused ? L.fus_wb_off : L.wb_off), nullptr,
-                            nullptr, (o.bwd_mask && !bits) ? net->act(o.src) : nullptr, net->grad(o.src), s);
-        };
+        auto run = [&]() { return launch_conv_site(net, o, dir, b, ids[k], s); };
         if (run() != IVF_OK) continue;          // variant not applicable to this shape
         (void)hipEventRecord(e0, s);
         for (int r = 0; r < reps; ++r) (void)run();

@@ -42,7 +42,7 @@ void prof_name(int variant, const char* fmt, ...) {
   vsnprintf(g_prof_names[variant], sizeof(g_prof_names[variant]), fmt, ap);
   va_end(ap);
 }
-void prof_set_iteration(int it) { g_prof.active = g_prof.enabled && it >= 0 && (it % g_prof.every == 0); }
+void prof_set_iteration(int it) { g_prof.active = g_prof.enabled && (g_prof.every == 0 || (it >= 0 && it % g_prof.every == 0)); }
 void prof_set_flops(double f) { g_prof.next_flops = f; }
 void prof_set_site(int site) { g_prof.next_site = site; }
 bool prof_begin(hipStream_t s, int variant) {
@@ -71,9 +71,9 @@ void prof_end(hipStream_t s) {
 }  // namespace ivf
 
 extern "C" int ivf_profile_enable(int every, int max_launches) {
-  IVF_CHECK_ARG(every >= 1 && max_launches > 0, "profile_enable: bad args");
+  IVF_CHECK_ARG(every >= 0 && max_launches > 0, "profile_enable: bad args");
   ivf::g_prof.enabled = true;
-  ivf::g_prof.active = false;
+  ivf::g_prof.active = every == 0;   // every = 0: each convolution launch, inside a search or not
   ivf::g_prof.every = every;
   ivf::g_prof.cap = (size_t)max_launches;
   ivf::g_prof.used = 0;

@@ -20,6 +20,7 @@ class IvfError(RuntimeError):
 
 
 MATH_FP32, MATH_BF16X3, MATH_BF16X6, MATH_BF16ACT = 0, 1, 2, 3
+CONV_AUTO, CONV_IGEMM_BASE, CONV_PIX4, CONV_HALO_BASE = 0, 1, 15, 16      # IVF_CONV_* (kernel variant ids)
 MATH_MODES = {"fp32": MATH_FP32, "bf16x3": MATH_BF16X3, "bf16x6": MATH_BF16X6, "bf16act": MATH_BF16ACT}
 
 
@@ -127,6 +128,7 @@ _SIGS = {
     "ivf_i3d_gradcam_layer": (c_int, [_P, _P, _I, _P, c_char_p, _I, _I, _I, _P, _P, _P]),
     "ivf_i3d_conv_flops_per_clip": (ctypes.c_double, [_P]),
     "ivf_conv3d_variants": (c_int, [POINTER(ConvDesc), POINTER(c_int), _I]),
+    "ivf_conv3d_default_variant": (c_int, [POINTER(ConvDesc)]),
     "ivf_i3d_num_conv_ops": (c_int, [_P]),
     "ivf_i3d_autotune": (c_int, [_P, _I, _I, _P]),
     "ivf_i3d_get_tuning": (c_int, [_P, POINTER(c_int)]),

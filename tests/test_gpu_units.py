@@ -723,7 +723,7 @@ def test_bf16_activation_stem_ends_keep_fp32():
     d.pT, d.pH, d.pW = [p[0] for p in pads]
     d.relu, d.math = 1, mm
     ids = (ctypes.c_int * 96)()
-    assert lib.ivf_conv3d_variants(ctypes.byref(d), ids, 96) == 1 and ids[0] == 15      # IVF_CONV_PIX4
+    assert lib.ivf_conv3d_variants(ctypes.byref(d), ids, 96) == 1 and ids[0] == L.CONV_PIX4
     y = torch.full((B,) + tuple(outs) + (cout,), float('nan'), dtype=torch.bfloat16, device='cuda')
     L.check(lib.ivf_conv3d(ctypes.byref(d), L.ptr(xcl), L.ptr(wf), L.ptr(scd), L.ptr(shd), None, L.ptr(y), L.stream()))
     want = torch.relu(y_ref).detach().permute(0, 2, 3, 4, 1)
@@ -753,7 +753,7 @@ def test_bf16_activation_stem_ends_keep_fp32():
     e.dT, e.dH, e.dW = thw
     e.dC = cinp
     n = lib.ivf_conv3d_variants(ctypes.byref(e), ids, 96)
-    assert n >= 3 and all(v >= 16 for v in list(ids)[:n])          # LDS-halo variants only
+    assert n >= 3 and all(v >= L.CONV_HALO_BASE for v in list(ids)[:n])          # LDS-halo variants only
     gcl = gy.cuda().contiguous()
     ran = 0
     for v in list(ids)[:n]:
@@ -817,3 +817,79 @@ def test_every_stem_backward_variant_matches_torch(math):
         assert rel_err(from_cl(dxcl, cin).double().cpu().numpy(), dx_ref.numpy()) < (1e-4 if math == "bf16x3" else 1e-5), \
             f"variant {v}"
     assert ran >= 8
+
+
+def _auto_and_default_variant(k, s, cin, cout, thw, math, seed):
+    """One conv launched with IVF_CONV_AUTO and with the id ivf_conv3d_default_variant names: returns that id after
+    checking that both outputs are equal bit for bit and that the launch profiler saw both launches in the id's class."""
+    import ivf_arch as arch
+    import ivf_lib as L
+    lib = L.lib()
+    gen = torch.Generator().manual_seed(seed)
+    mm = L.MATH_MODES[math]
+    cinp = (cin + 3) // 4 * 4
+    pads = [arch.same_pad(n, k, s)[0] for n in thw]
+    outs = [arch.out_size(n, k, s) for n in thw]
+    x = to_cl(torch.randn((1, cin) + thw, generator=gen).cuda(), cinp)
+    if math == "bf16act" and not (cinp == 4 and s == 2):       # (the stem reads fp32 pixels)
+        x = x.bfloat16()
+    wd = (torch.randn(cout, cin, k, k, k, generator=gen) * 0.1).cuda()
+    wf = torch.empty(lib.ivf_conv3d_pack_fwd_elems(cout, cinp, k, k, k, mm), device='cuda')
+    L.check(lib.ivf_conv3d_pack_fwd(L.ptr(wd), L.ptr(wf), cout, cin, cinp, k, k, k, mm, L.stream()))
+    d = L.ConvDesc()
+    d.B, d.Ti, d.Hi, d.Wi = 1, *thw
+    d.Cin, d.in_ld, d.in_coff = cinp, cinp, 0
+    d.To, d.Ho, d.Wo = outs
+    d.Cout, d.out_ld, d.out_coff = cout, cout, 0
+    d.kT = d.kH = d.kW = k
+    d.sT = d.sH = d.sW = s
+    d.pT, d.pH, d.pW = pads
+    d.relu, d.math = 1, mm
+    vid = lib.ivf_conv3d_default_variant(ctypes.byref(d))
+    assert vid > 0, lib.ivf_last_error()
+    # profiler class of a variant: its id; the split-bf16 kernels of the implicit-GEMM tiles sit 3 above the fp32 ones
+    cls = vid + (3 if L.CONV_IGEMM_BASE <= vid < L.CONV_PIX4 and math != "fp32" else 0)
+    ys = []
+    ms, cnt, fl = (ctypes.c_double * 96)(), (ctypes.c_longlong * 96)(), (ctypes.c_double * 96)()
+    L.check(lib.ivf_profile_enable(0, 8))
+    try:
+        for v in (L.CONV_AUTO, vid):
+            d.variant = v
+            y = torch.full((1,) + tuple(outs) + (cout,), float('nan'), device='cuda',
+                           dtype=torch.bfloat16 if math == "bf16act" else torch.float32)
+            L.check(lib.ivf_conv3d(ctypes.byref(d), L.ptr(x), L.ptr(wf), None, None, None, L.ptr(y), L.stream()))
+            ys.append(y)
+        L.check(lib.ivf_profile_collect(ms, cnt, fl))
+    finally:
+        lib.ivf_profile_disable()
+    assert cnt[cls] == 2 and sum(cnt) == 2, f"variant {vid}: launches per class {dict((i, c) for i, c in enumerate(cnt) if c)}"
+    bits = torch.int16 if math == "bf16act" else torch.int32
+    assert not torch.isnan(ys[0]).any() and ys[0].abs().max() > 0
+    assert torch.equal(ys[0].view(bits), ys[1].view(bits)), f"variant {vid}"
+    return vid
+
+
+@pytest.mark.parametrize("math,ids", [("bf16x3", {0, 8, 1, 9, 3, 10, 5, 11, 7, 12}), ("bf16act", {0, 8, 1, 9, 3, 10, 5, 11, 7, 12}),
+                                      ("bf16x6", {68, 18, 61, 9, 20, 10, 21, 11, 37, 12})])
+def test_auto_launch_is_the_default_halo_tile(math, ids):
+    """IVF_CONV_AUTO and the id of ivf_conv3d_default_variant are the same launch.  3x3x3 convs whose output widths pick
+    the 192-, 128-, 96-, 64- and 32-column tiles on a 4-frame and a 2-frame map: every built-in LDS-halo tile of the mode."""
+    import ivf_lib as L
+    seen = set()
+    for to in (4, 2):
+        for cout in (32, 64, 96, 128, 192):
+            vid = _auto_and_default_variant(3, 1, 16, cout, (to, 8, 8), math, 100 + cout + to)
+            assert vid >= L.CONV_HALO_BASE
+            seen.add(vid - L.CONV_HALO_BASE)
+    assert seen == ids
+
+
+@pytest.mark.parametrize("math", ["fp32", "bf16x3"])
+def test_auto_launch_is_the_default_gemm_or_stem_kernel(math):
+    """The same for the implicit GEMM (1x1x1; fewest padded columns: Cout 40 -> the 64-column tile, 200 -> the 32-column
+    tile) and the 7x7x7 stride-2 4-channel stem (fp32: the 64-column implicit-GEMM tile, split-bf16: the pix4 kernel)."""
+    import ivf_lib as L
+    assert _auto_and_default_variant(1, 1, 16, 40, (2, 8, 8), math, 7) == L.CONV_IGEMM_BASE + 1
+    assert _auto_and_default_variant(1, 1, 16, 200, (2, 8, 8), math, 8) == L.CONV_IGEMM_BASE + 2
+    stem = _auto_and_default_variant(7, 2, 3, 64, (8, 16, 16), math, 9)
+    assert stem == (L.CONV_IGEMM_BASE + 1 if math == "fp32" else L.CONV_PIX4)
