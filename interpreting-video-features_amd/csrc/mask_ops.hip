@@ -50,10 +50,15 @@ __global__ void freeze_fwd_kernel(const float* __restrict__ x, const float* __re
 }
 
 // channels-last variant: one thread per (b, pixel) handles all C channels and
-// writes one 16-byte vector per frame (C <= 4, cpad == 4)
-__global__ void freeze_fwd_cl4_kernel(const float* __restrict__ x, const float* __restrict__ mask,
-                                      float* __restrict__ p, int B, int C, int T, int HW,
-                                      int mask_per_clip) {
+// writes one 16-byte vector per frame (C <= 4, cpad == 4).  TT > 0: T == TT known at compile time -- every frame of
+// the pixel (and the mask) is requested before the scan goes over them, as in freeze_bwd_kernel; with the run-time
+// `u < T` loop each load is used in the body that issues it, T serial round trips per thread.  TT == 0: that loop,
+// any T.
+// The arithmetic and its order are the same in both.
+template <int TT>   // 0, or a multiple of 16
+__global__ __launch_bounds__(256) void freeze_fwd_cl4_kernel(const float* __restrict__ x, const float* __restrict__ mask,
+                                                             float* __restrict__ p, int B, int C, int T, int HW,
+                                                             int mask_per_clip) {
   size_t total = (size_t)B * HW;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total;
        i += (size_t)gridDim.x * blockDim.x) {
@@ -61,16 +66,45 @@ __global__ void freeze_fwd_cl4_kernel(const float* __restrict__ x, const float* 
     int b = i / HW;
     const float* mp = mask + (mask_per_clip ? (size_t)b * T : 0);
     float prev[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int u = 0; u < T; ++u) {
-      float m = u ? mp[u] : 0.f;
-      float v[4] = {0.f, 0.f, 0.f, 0.f};
-      for (int c = 0; c < C; ++c) {
-        float xv = x[((size_t)(b * C + c) * T + u) * HW + px];
-        v[c] = u ? (1.f - m) * xv + m * prev[c] : xv;
-        prev[c] = v[c];
+    if constexpr (TT > 0) {
+      // 16 frames at a time (T = 32 in one piece takes every register of the wave: one wave per SIMD)
+#pragma unroll 1
+      for (int u0 = 0; u0 < TT; u0 += 16) {
+        float xv[4][16], m[16];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+          for (int j = 0; j < 16; ++j) {
+            xv[c][j] = 0.f;
+            if (c < C) xv[c][j] = x[((size_t)(b * C + c) * TT + u0 + j) * HW + px];
+          }
+#pragma unroll
+        for (int j = 0; j < 16; ++j) m[j] = u0 + j ? mp[u0 + j] : 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (c < C) {
+              v[c] = u0 + j ? (1.f - m[j]) * xv[c][j] + m[j] * prev[c] : xv[c][j];
+              prev[c] = v[c];
+            }
+          *reinterpret_cast<float4*>(p + ((size_t)(b * TT + u0 + j) * HW + px) * 4) =
+              make_float4(v[0], v[1], v[2], v[3]);
+        }
       }
-      *reinterpret_cast<float4*>(p + ((size_t)(b * T + u) * HW + px) * 4) =
-          make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+      for (int u = 0; u < T; ++u) {
+        float m = u ? mp[u] : 0.f;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < C; ++c) {
+          float xv = x[((size_t)(b * C + c) * T + u) * HW + px];
+          v[c] = u ? (1.f - m) * xv + m * prev[c] : xv;
+          prev[c] = v[c];
+        }
+        *reinterpret_cast<float4*>(p + ((size_t)(b * T + u) * HW + px) * 4) =
+            make_float4(v[0], v[1], v[2], v[3]);
+      }
     }
   }
 }
@@ -506,8 +540,13 @@ extern "C" int ivf_freeze_fwd(const float* x, const float* mask, float* p, int B
   IVF_CHECK_ARG(out_cpad == 0 || out_cpad >= C, "freeze_fwd: out_cpad (%d) < C (%d)", out_cpad, C);
   hipStream_t s = (hipStream_t)stream;
   if (out_cpad == 4 && C <= 4) {
-    hipLaunchKernelGGL(freeze_fwd_cl4_kernel, dim3(grid_for((size_t)B * HW, 256, 2048)), dim3(256), 0, s, x, mask,
-                       p, B, C, T, HW, mask_per_clip);
+    const dim3 grid(grid_for((size_t)B * HW, 256, 2048)), block(256);
+    if (T == 16)
+      hipLaunchKernelGGL(freeze_fwd_cl4_kernel<16>, grid, block, 0, s, x, mask, p, B, C, T, HW, mask_per_clip);
+    else if (T == 32)
+      hipLaunchKernelGGL(freeze_fwd_cl4_kernel<32>, grid, block, 0, s, x, mask, p, B, C, T, HW, mask_per_clip);
+    else
+      hipLaunchKernelGGL(freeze_fwd_cl4_kernel<0>, grid, block, 0, s, x, mask, p, B, C, T, HW, mask_per_clip);
   } else {
     if (out_cpad > C) {
       // pad channels must read as zero for the conv that consumes them

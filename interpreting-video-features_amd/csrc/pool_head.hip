@@ -46,7 +46,7 @@ template <class T>
 __global__ void maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
                                    unsigned char* __restrict__ idx, PoolArgs a, int nbx) {
   // workgroup = a block of one output row's (w, 4-channel group) cells; rows, then clip frames: see
-  // maxpool_bwd_fixed_kernel; numbered so that every XCD owns a contiguous run of rows (the input rows two output
+  // maxpool_bwd_fixed16_kernel; numbered so that every XCD owns a contiguous run of rows (the input rows two output
   // rows share then meet in one L2: 0-11 % faster than the round-robin deal, most on the 3x3x3 / (2,2,2) pool)
   const unsigned C4 = (unsigned)a.C >> 2;
   unsigned blk = (unsigned)xcd_remap((int)blockIdx.x, (int)gridDim.x);
@@ -240,101 +240,136 @@ __global__ void maxpool_bwd_kernel(const T* __restrict__ dy, const unsigned char
   }
 }
 
-// backward for the strided pools with the window geometry known at compile time: at most
-// ceil(k/s) outputs per dimension cover an input cell (2 x 2 for the 1x3x3 / (1,2,2) pools),
-// so every candidate's (dY, arg-max) load is issued up front, unconditionally predicated --
-// no dependent loops, neighbouring cells' re-reads come from L1.  One thread per input cell
-// and 4 channels; contributions are added in ascending (to, ho, wo) order like everywhere else.
+// backward for the strided pools with the window geometry known at compile time, by stride-aligned blocks: in padded
+// coordinates n = i + pad the ST x SH x SW cells n = q*S .. q*S + S-1 of a block are covered by the same
+// ceil(k/s) windows per dimension, o = q - (N-1) .. q, and a cell's tap in each of them, k = n - o*S, is a
+// compile-time constant.  One thread owns a block and 4 channels: it requests the (dY, arg-max) of those windows once
+// (2 x 2 for the 1x3x3 / (1,2,2) pools, where one thread per CELL asked for them 4+2+2+1 = 9 times; 8 against 27 for
+// 3x3x3 / (2,2,2)), with the old dX / ReLU mask of its cells, before any is used, then sums per cell the windows
+// whose recorded tap is that cell's, in ascending (to, ho, wo) order like everywhere else, and stores 16 bytes per
+// cell.  Windows outside the output are not loaded and match nothing; cells outside the map (front padding, a
+// partial last block) are not stored.
 template <class T, int KT, int KH, int KW, int ST, int SH, int SW>
 __global__ __launch_bounds__(256) void maxpool_bwd_fixed_kernel(const T* __restrict__ dy,
                                                                 const unsigned char* __restrict__ idx,
                                                                 T* __restrict__ dx,
                                                                 const T* __restrict__ relu_mask, int accumulate,
-                                                                PoolArgs a) {
+                                                                PoolArgs a, int nbt, int nbh, int nbw) {
   constexpr int NT = (KT + ST - 1) / ST, NH = (KH + SH - 1) / SH, NW = (KW + SW - 1) / SW;
-  // grid (blocks of one image row's (w, 4-channel group) cells, h, clip * frame): the row coordinates come from the
-  // block index on the scalar unit, one 32-bit division per thread is left (a flat 64-bit index cost five 64-bit
-  // divisions per thread: this kernel ran at 2.6 TB/s beside a forward at 4.8 over the same bytes).
-  // (Numbering the workgroups so that each XCD owns a contiguous run of rows -- as the forward does -- was measured in
-  // round 3: 5 % SLOWER here; the kernel already moves its compulsory bytes at 4.5-4.7 TB/s.)
+  // grid (blocks of (h-block, w-block, 4-channel group), clip * t-block): lanes run over channels first, so a wave's
+  // stores to one cell row of its blocks are runs of 16 * C4 bytes (whole 128-byte lines from C = 32 up), SW * that
+  // apart, and the store of the next dw fills the gaps; two 32-bit divisions per thread for SH * SW * ST cells.
   const unsigned C4 = (unsigned)a.C >> 2;
-  const unsigned r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= (unsigned)a.Wi * C4) return;
-  const int wi = (int)(r / C4);
-  const int c4 = (int)(r - (unsigned)wi * C4);
-  const int hi = blockIdx.y;
-  const int ti = (int)(blockIdx.z % (unsigned)a.Ti);
-  const int b = (int)(blockIdx.z / (unsigned)a.Ti);
-  const size_t m = ((size_t)(b * a.Ti + ti) * a.Hi + hi) * a.Wi + wi;
-  const int nt = ti + a.pT, nh = hi + a.pH, nw = wi + a.pW;
+  unsigned r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= (unsigned)nbh * (unsigned)nbw * C4) return;
+  const int c4 = (int)(r % C4); r /= C4;
+  const int qw = (int)(r % (unsigned)nbw) + a.pW / SW;
+  const int qh = (int)(r / (unsigned)nbw) + a.pH / SH;
+  const int qt = (int)(blockIdx.y % (unsigned)nbt) + a.pT / ST;
+  const int b = (int)(blockIdx.y / (unsigned)nbt);
   float4 g[NT][NH][NW];
   unsigned u[NT][NH][NW];
-  // candidate j along a dim: output o = n/s - (N-1-j) (ascending in j), tap k = n - o*s
 #pragma unroll
   for (int jt = 0; jt < NT; ++jt) {
-    const int to = nt / ST - (NT - 1 - jt), kt = nt - to * ST;
+    const int to = qt - (NT - 1 - jt);
 #pragma unroll
     for (int jh = 0; jh < NH; ++jh) {
-      const int ho = nh / SH - (NH - 1 - jh), kh = nh - ho * SH;
+      const int ho = qh - (NH - 1 - jh);
 #pragma unroll
       for (int jw = 0; jw < NW; ++jw) {
-        const int wo = nw / SW - (NW - 1 - jw), kw = nw - wo * SW;
-        const bool ok = to >= 0 && to < a.To && kt < KT && ho >= 0 && ho < a.Ho && kh < KH && wo >= 0 &&
-                        wo < a.Wo && kw < KW;
+        const int wo = qw - (NW - 1 - jw);
         g[jt][jh][jw] = make_float4(0.f, 0.f, 0.f, 0.f);
-        u[jt][jh][jw] = 0xffffffffu;
-        if (ok) {
+        u[jt][jh][jw] = 0xffffffffu;   // matches no tap, like the dead-window code 255
+        if ((unsigned)to < (unsigned)a.To && (unsigned)ho < (unsigned)a.Ho && (unsigned)wo < (unsigned)a.Wo) {
           const size_t mo = ((size_t)(b * a.To + to) * a.Ho + ho) * a.Wo + wo;
           g[jt][jh][jw] = ld4(dy + mo * a.out_ld + a.out_coff + 4 * c4);
-          // compare against this cell's tap: store (recorded tap XOR own tap), zero byte = match
-          const unsigned tap = (unsigned)((kt * KH + kh) * KW + kw);
-          u[jt][jh][jw] = *reinterpret_cast<const unsigned*>(idx + mo * a.C + 4 * c4) ^ (tap * 0x01010101u);
+          u[jt][jh][jw] = *reinterpret_cast<const unsigned*>(idx + mo * a.C + 4 * c4);
         }
       }
     }
   }
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  bool live[ST][SH][SW];
+  float4 old[ST][SH][SW], gate[ST][SH][SW];
 #pragma unroll
-  for (int jt = 0; jt < NT; ++jt)
+  for (int dt = 0; dt < ST; ++dt)
 #pragma unroll
-    for (int jh = 0; jh < NH; ++jh)
+    for (int dh = 0; dh < SH; ++dh)
 #pragma unroll
-      for (int jw = 0; jw < NW; ++jw) {
-        const unsigned x = u[jt][jh][jw];
-        const float4 v = g[jt][jh][jw];
-        if ((x & 0x000000ffu) == 0u) acc[0] += v.x;
-        if ((x & 0x0000ff00u) == 0u) acc[1] += v.y;
-        if ((x & 0x00ff0000u) == 0u) acc[2] += v.z;
-        if ((x & 0xff000000u) == 0u) acc[3] += v.w;
+      for (int dw = 0; dw < SW; ++dw) {
+        const int ti = qt * ST + dt - a.pT, hi = qh * SH + dh - a.pH, wi = qw * SW + dw - a.pW;
+        live[dt][dh][dw] = (unsigned)ti < (unsigned)a.Ti && (unsigned)hi < (unsigned)a.Hi && (unsigned)wi < (unsigned)a.Wi;
+        old[dt][dh][dw] = make_float4(0.f, 0.f, 0.f, 0.f);
+        gate[dt][dh][dw] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live[dt][dh][dw]) {
+          const size_t off = (((size_t)(b * a.Ti + ti) * a.Hi + hi) * a.Wi + wi) * a.in_ld + a.in_coff + 4 * c4;
+          if (accumulate) old[dt][dh][dw] = ld4(dx + off);
+          if (relu_mask) gate[dt][dh][dw] = ld4(relu_mask + off);
+        }
       }
-  T* dst = dx + m * a.in_ld + a.in_coff + 4 * c4;
-  if (accumulate) {
-    float4 o = ld4(dst);
-    acc[0] += o.x; acc[1] += o.y; acc[2] += o.z; acc[3] += o.w;
-  }
-  if (relu_mask) {
-    float4 k = ld4(relu_mask + m * a.in_ld + a.in_coff + 4 * c4);
-    if (!(k.x > 0.f)) acc[0] = 0.f;
-    if (!(k.y > 0.f)) acc[1] = 0.f;
-    if (!(k.z > 0.f)) acc[2] = 0.f;
-    if (!(k.w > 0.f)) acc[3] = 0.f;
-  }
-  st4(dst, make_float4(acc[0], acc[1], acc[2], acc[3]));
+#pragma unroll
+  for (int dt = 0; dt < ST; ++dt)
+#pragma unroll
+    for (int dh = 0; dh < SH; ++dh)
+#pragma unroll
+      for (int dw = 0; dw < SW; ++dw) {
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int jt = 0; jt < NT; ++jt) {
+          const int kt = dt + (NT - 1 - jt) * ST;
+#pragma unroll
+          for (int jh = 0; jh < NH; ++jh) {
+            const int kh = dh + (NH - 1 - jh) * SH;
+#pragma unroll
+            for (int jw = 0; jw < NW; ++jw) {
+              const int kw = dw + (NW - 1 - jw) * SW;
+              if (kt < KT && kh < KH && kw < KW) {   // (after unrolling: known at compile time)
+                const unsigned tap = (unsigned)((kt * KH + kh) * KW + kw);
+                const unsigned x = u[jt][jh][jw];
+                const float4 v = g[jt][jh][jw];
+                if ((x & 0xffu) == tap) acc[0] += v.x;
+                if (((x >> 8) & 0xffu) == tap) acc[1] += v.y;
+                if (((x >> 16) & 0xffu) == tap) acc[2] += v.z;
+                if ((x >> 24) == tap) acc[3] += v.w;
+              }
+            }
+          }
+        }
+        if (!live[dt][dh][dw]) continue;
+        if (accumulate) {
+          const float4 o = old[dt][dh][dw];
+          acc[0] += o.x; acc[1] += o.y; acc[2] += o.z; acc[3] += o.w;
+        }
+        if (relu_mask) {
+          const float4 k = gate[dt][dh][dw];
+          if (!(k.x > 0.f)) acc[0] = 0.f;
+          if (!(k.y > 0.f)) acc[1] = 0.f;
+          if (!(k.z > 0.f)) acc[2] = 0.f;
+          if (!(k.w > 0.f)) acc[3] = 0.f;
+        }
+        const int ti = qt * ST + dt - a.pT, hi = qh * SH + dh - a.pH, wi = qw * SW + dw - a.pW;
+        st4(dx + (((size_t)(b * a.Ti + ti) * a.Hi + hi) * a.Wi + wi) * a.in_ld + a.in_coff + 4 * c4,
+            make_float4(acc[0], acc[1], acc[2], acc[3]));
+      }
 }
+
+// blocks along one dimension: the padded coordinates p .. p + n - 1 of the map's cells fall into blocks p/s .. (p+n-1)/s
+static inline int pool_bwd_blocks(int n, int p, int s) { return (p + n - 1) / s - p / s + 1; }
 
 template <class T, int KT, int KH, int KW, int ST, int SH, int SW>
 static bool launch_pool_bwd_fixed(const PoolArgs& a, const T* dy, const unsigned char* idx, T* dx,
                                   const T* relu_mask, int accumulate, hipStream_t s) {
   if (a.kT != KT || a.kH != KH || a.kW != KW || a.sT != ST || a.sH != SH || a.sW != SW) return false;
-  if (a.Hi > 65535 || (long)a.B * a.Ti > 65535) return false;
-  hipLaunchKernelGGL((maxpool_bwd_fixed_kernel<T, KT, KH, KW, ST, SH, SW>),
-                     dim3((unsigned)cdiv((long)a.Wi * (a.C / 4), 256), (unsigned)a.Hi, (unsigned)(a.B * a.Ti)), dim3(256), 0, s,
-                     dy, idx, dx, relu_mask, accumulate, a);
+  if (a.pT < 0 || a.pH < 0 || a.pW < 0) return false;
+  const int nbt = pool_bwd_blocks(a.Ti, a.pT, ST), nbh = pool_bwd_blocks(a.Hi, a.pH, SH), nbw = pool_bwd_blocks(a.Wi, a.pW, SW);
+  const long nx = ((long)nbh * nbw * (a.C / 4) + 255) / 256;
+  if (nx >= 0x7fffffL || (long)a.B * nbt > 65535) return false;   // (the thread index is 32-bit)
+  hipLaunchKernelGGL((maxpool_bwd_fixed_kernel<T, KT, KH, KW, ST, SH, SW>), dim3((unsigned)nx, (unsigned)(a.B * nbt)), dim3(256), 0, s,
+                     dy, idx, dx, relu_mask, accumulate, a, nbt, nbh, nbw);
   return true;
 }
 
-// The same backward with 16 bytes of channels per lane and every candidate's RAW bits requested first (bf16 storage:
-// 8 channels per thread halve the instructions per byte; measured on fp32 the form above is faster, so it keeps it).
+// The backward of bf16 storage: one thread per input CELL and 16 bytes of channels (8 channels per thread halve the
+// instructions per byte), every candidate's RAW bits requested first.
 // backward for the strided pools with the window geometry known at compile time: at most
 // ceil(k/s) outputs per dimension cover an input cell (2 x 2 for the 1x3x3 / (1,2,2) pools),
 // so every candidate's (dY, arg-max) load is issued up front, unconditionally predicated --
@@ -761,56 +796,71 @@ static int pool_3s1_groups(const PoolArgs& a) {
 }
 
 // ---------------------------------------------------------------- head
-// One block per clip.  pooled[c] = mean over the npos feature cells;
-// logits[k] = bias[k] + sum_c pooled[c] W[k][c]; probs = softmax(logits).
+// pooled[c] = mean over the npos feature cells; logits[k] = bias[k] + sum_c pooled[c] W[k][c];
+// probs = softmax(logits).  Grid (clip, slice of `kper` classes): every workgroup recomputes the pooled vector of its
+// clip (npos x C reads; the slices of a clip are numbered B apart, i.e. meet in one L2 when B is a multiple of the
+// XCD count) and produces its classes, one wave per logit -- one workgroup per clip left 7/8 of the chip idle and
+// each wave walking K/16 logits.  Every sum keeps its order: channels over p ascending, a logit as 64 strided lane
+// partials folded by the shuffle tree.
 template <class T>
 __global__ __launch_bounds__(1024) void head_fwd_kernel(
     const T* __restrict__ feat, const float* __restrict__ w, const float* __restrict__ bias,
-    float* __restrict__ pooled_out, float* __restrict__ logits, float* __restrict__ probs, int npos,
-    int C, int K, int softmax) {
-  extern __shared__ float sm[];  // C pooled + K logits + 8 scratch
+    float* __restrict__ pooled_out, float* __restrict__ logits, float* __restrict__ probs_copy, int npos,
+    int C, int K, int kper) {
+  extern __shared__ float sm[];  // C pooled
   float* pooled = sm;
-  float* lg = sm + C;
-  float* red = lg + K;
   const int b = blockIdx.x;
+  const int k0 = blockIdx.y * kper, k1 = min(k0 + kper, K);
   const T* f = feat + (size_t)b * npos * C;
   const float inv = 1.f / (float)npos;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     float s = 0.f;
     for (int p = 0; p < npos; ++p) s += ld1(f + (size_t)p * C + c);
     pooled[c] = s * inv;
-    if (pooled_out) pooled_out[(size_t)b * C + c] = s * inv;
+    if (pooled_out && blockIdx.y == 0) pooled_out[(size_t)b * C + c] = s * inv;
   }
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int k = wave; k < K; k += nw) {
+  for (int k = k0 + wave; k < k1; k += nw) {
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += pooled[c] * w[(size_t)k * C + c];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
     if (lane == 0) {
       s += bias ? bias[k] : 0.f;
-      lg[k] = s;
       logits[(size_t)b * K + k] = s;
+      if (probs_copy) probs_copy[(size_t)b * K + k] = s;   // softmax off: probs = logits
     }
   }
+}
+
+// softmax over the K logits of a clip, one workgroup per clip, in the serial kernel's order: thread 0 takes the
+// maximum and adds the exponentials left to right (a tree would change the sum); the expf calls themselves, which
+// were the serial part, run one per thread in between.
+__global__ __launch_bounds__(256) void head_softmax_kernel(const float* __restrict__ logits, float* __restrict__ probs,
+                                                           int K) {
+  extern __shared__ float sm[];  // K logits + K exponentials + 2 scratch
+  float* lg = sm;
+  float* ex = sm + K;
+  float* red = ex + K;
+  const int b = blockIdx.x;
+  for (int k = threadIdx.x; k < K; k += blockDim.x) lg[k] = logits[(size_t)b * K + k];
   __syncthreads();
-  if (!probs) return;
-  if (!softmax) {
-    for (int k = threadIdx.x; k < K; k += blockDim.x) probs[(size_t)b * K + k] = lg[k];
-    return;
-  }
   if (threadIdx.x == 0) {
     float mx = -INFINITY;
     for (int k = 0; k < K; ++k) mx = fmaxf(mx, lg[k]);
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) s += expf(lg[k] - mx);
     red[0] = mx;
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < K; k += blockDim.x) ex[k] = expf(lg[k] - red[0]);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s += ex[k];
     red[1] = s;
   }
   __syncthreads();
-  for (int k = threadIdx.x; k < K; k += blockDim.x)
-    probs[(size_t)b * K + k] = expf(lg[k] - red[0]) / red[1];
+  for (int k = threadIdx.x; k < K; k += blockDim.x) probs[(size_t)b * K + k] = ex[k] / red[1];
 }
 
 // backward to the feature map from an upstream gradient on the head output:
@@ -1081,8 +1131,8 @@ extern "C" int ivf_maxpool3d_fwd(const ivf_pool3d_desc* d, const void* x, void* 
 // Backward, the same three cases (figures: DESIGN section 7, "Pools" and item 10):
 //  1. 3x3x3 stride-1 'same', W <= 256: the separable gather (fp32 779 us, bf16 772 us on Mixed_3c's pool at B=64);
 //  2. a (window, stride) pair of the table: 2-byte storage with 8-aligned channel geometry takes the 16-byte-lane
-//     kernel (750 -> 538 us on MaxPool3d_2a), everything else the 4-channel one (fp32 measured faster in that form,
-//     827 vs 903 us; 4.5-4.7 TB/s of its compulsory bytes);
+//     kernel, one thread per cell (750 -> 538 us on MaxPool3d_2a); everything else the 4-channel one by
+//     stride-aligned blocks (fp32 at B=32: MaxPool3d_2a + 3a 670 -> 367 us, MaxPool3d_4a 190 -> 106 us);
 //  3. anything else, or a grid beyond the launch limits: the generic grid-stride gather.
 template <class T>
 static int pool_bwd_impl(const PoolArgs& a, const T* dy, const unsigned char* argmax, T* dx, const T* relu_mask,
@@ -1131,12 +1181,20 @@ template <class T>
 static int head_fwd_impl(const T* feat, const float* w, const float* bias, float* pooled, float* logits, float* probs, int B,
                          int npos, int C, int K, int softmax, ivf_stream_t stream) {
   IVF_CHECK_ARG(feat && w && logits, "head_fwd: null pointer");
-  IVF_CHECK_ARG(B > 0 && npos > 0 && C > 0 && K > 0 && (size_t)(C + K + 8) * 4 <= 64 * 1024,
+  IVF_CHECK_ARG(B > 0 && npos > 0 && C > 0 && K > 0 && (size_t)(C + K + 8) * 4 <= 64 * 1024 &&
+                    (size_t)(2 * K + 2) * 4 <= 64 * 1024,
                 "head_fwd: bad dims");
-  size_t shm = (size_t)(C + K + 8) * sizeof(float);
-  hipLaunchKernelGGL((head_fwd_kernel<T>), dim3(B), dim3(1024), shm, (hipStream_t)stream, feat, w, bias, pooled,
-                     logits, probs, npos, C, K, softmax);
+  // two logits per wave of the 1024-thread workgroup: 6 slices for K = 174, 192 workgroups at B = 32
+  const int kper = 32, slices = cdiv(K, kper);
+  IVF_CHECK_ARG(B <= 0x7fffffff && slices <= 65535, "head_fwd: grid too large");
+  hipLaunchKernelGGL((head_fwd_kernel<T>), dim3(B, slices), dim3(1024), (size_t)C * sizeof(float), (hipStream_t)stream,
+                     feat, w, bias, pooled, logits, (probs && !softmax) ? probs : nullptr, npos, C, K, kper);
   IVF_CHECK_LAUNCH();
+  if (probs && softmax) {
+    hipLaunchKernelGGL(head_softmax_kernel, dim3(B), dim3(256), (size_t)(2 * K + 2) * sizeof(float), (hipStream_t)stream,
+                       logits, probs, K);
+    IVF_CHECK_LAUNCH();
+  }
   return IVF_OK;
 }
 
