@@ -139,6 +139,51 @@ int ivf_blob_select(const float* scores, const float* orig, const float* full, i
                     float lam2, float threshold, int* best, float* best_obj, float* obj, int* minimal,
                     ivf_stream_t stream);
 
+/* ------------------------------------------------------------------ spatio-temporal masks (maskType 'spacetime')
+ * An EXTENSION with no counterpart in the reference, pinned by torch autograd on the reference's models:
+ * the freeze perturbation with a mask value per pixel and frame, parametrised per frame on a coarse gh x gw grid
+ * (gh, gw <= 32).  S = sigmoid(R), R [B,T,gh,gw];  M[b,t] = A_H S[b,t] A_W^T, M [B,T,H,W];
+ * P[0] = X[0], P[u] = (1 - M[u]) X[u] + M[u] P[u-1] per pixel.  No float atomics: every sum has a fixed order and a
+ * clip's results do not depend on the batch it ran in.
+ *
+ * ivf_stmask_axis_weights: HOST.  A [n_out,n_in] = G U in fp64, rounded once to fp32: U bilinear upsampling with
+ * half-pixel centres and clamped edges (F.interpolate(mode='bilinear', align_corners=False)), G a Gaussian of radius
+ * ceil(3 sigma) in output pixels, taps normalised to sum 1, replicated border; sigma == 0 gives A = U.  Entries >= 0,
+ * rows sum to 1. */
+int ivf_stmask_axis_weights(int n_out, int n_in, float sigma, float* A_host);
+/* M = A_H S A_W^T per (b,t): tmp[i][x] = sum_j S[i,j] A_W[x,j] (j ascending), M[y,x] = sum_i A_H[y,i] tmp[i][x]
+ * (i ascending).  A_H [H,gh], A_W [W,gw] on the device.  Any non-negative matrices do: H = W = 1 with the uniform
+ * rows A_H = 1/gh, A_W = 1/gw gives the spatial mean of S per frame, which is how the record's time_mask is made
+ * (ivf_search.MaskSearch._run_spacetime). */
+int ivf_stmask_expand_fwd(const float* S, const float* A_H, const float* A_W, float* M, int B, int T, int gh, int gw,
+                          int H, int W, ivf_stream_t stream);
+/* The exact adjoint, dS = A_H^T dM A_W, one pass over dM, one workgroup per (b,t). */
+int ivf_stmask_expand_bwd(const float* dM, const float* A_H, const float* A_W, float* dS, int B, int T, int gh, int gw,
+                          int H, int W, ivf_stream_t stream);
+/* Per-pixel freeze: x [B,C,T,HW] NCTHW, M [B,T,HW] in [0,1]; p as ivf_freeze_fwd names it (out_cpad 0 NCTHW, else
+ * channels-last rows of out_cpad >= C floats, pad lanes +0.0; 4 needs C <= 4).  The arithmetic and its order are
+ * those of ivf_freeze_fwd: a spatially constant M gives the same bits. */
+int ivf_stfreeze_fwd(const float* x, const float* M, float* p, int B, int C, int T, int HW, int out_cpad,
+                     ivf_stream_t stream);
+/* dM[b,u,px] = sum_c (P[u-1] - X[u]) G[u], c ascending, G the reverse scan of g (layout as ivf_freeze_bwd's g_cpad;
+ * pad lanes ignored); dM[:,0] = 0.0 exactly.  T <= 64.  No reduction across pixels, no workspace. */
+int ivf_stfreeze_bwd(const float* x, const float* M, const float* g, float* dM, int B, int C, int T, int HW, int g_cpad,
+                     ivf_stream_t stream);
+/* Regulariser: sig = sigmoid(raw); terms[b] = {lam1 sum S, lam2 TVt, lam3 TVs} / (gh gw) with
+ * TVt = sum_cells sum_{u=1}^{T-2} |S[u-1]-S[u]|^3 + |S[u+1]-S[u]|^3 (calc_tv_norm's `val`, mask.py:93-96, per cell,
+ * without its (.^(1/3))^3 chain: the identity in value, NaN in gradient at 0) and TVs the same cube over vertical and
+ * horizontal neighbours within a frame; dreg_dsig = d(sum of the three)/dsig.  One workgroup per clip. */
+int ivf_stmask_reg(const float* raw, int B, int T, int gh, int gw, float lam1, float lam2, float lam3, float* sig,
+                   float* terms, float* dreg_dsig, ivf_stream_t stream);
+/* Loop tail: traj_row[b] = (J, l1, tvt, tvs, score), J = l1 + tvt + tvs + score; chain through the sigmoid and the
+ * Adam step of ivf_search_step / ivf_adam_step on raw [B,T,gh,gw]. */
+int ivf_stmask_step(float* raw, const float* sig, const float* dscore_dsig, const float* dreg_dsig, const float* terms,
+                    const float* score, float* exp_avg, float* exp_avg_sq, float* traj_row, int B, int T, int gh, int gw,
+                    int step, float lr, float beta1, float beta2, float eps, ivf_stream_t stream);
+/* Bytes of caller-owned scratch of ivf_{i3d,clstm}_stsearch for b = B clips (M, dM, sig, dreg, dsig, terms, score);
+ * 0 with the message set for a shape the loop refuses. */
+size_t ivf_stsearch_workspace_bytes(int B, int T, int H, int W, int gh, int gw);
+
 /* Clip ingest: the arithmetic of ImLoader.__getitem__ /
  * KTHImLoader.__getitem__ after the JPEG decode (data_loader_jpg.py:29-37,
  * data_loader_kth.py:25-44): uint8 frames [B][T][H][W][C] -> float32 (exact), permuted to
@@ -412,6 +457,18 @@ int ivf_i3d_search(ivf_i3d_t* net, const float* x, int b, const int* target, flo
 int ivf_i3d_perturbed_forward(ivf_i3d_t* net, const float* x, int b, const float* mask, int mode,
                               float* probs, ivf_stream_t stream);
 
+/* Spatio-temporal mask search (extension, see ivf_stmask_*): N iterations on raw [b,T,gh,gw] with per-pixel freeze
+ * through this plan; A_H [H,gh], A_W [W,gw] from ivf_stmask_axis_weights, on the device; traj [N,b,5] (optional) =
+ * (J, l1, tvt, tvs, score); ws = ivf_stsearch_workspace_bytes(b, T, H, W, gh, gw) bytes from the caller, 256-byte
+ * aligned.  One stream, no host synchronisation, no allocation.  _stperturbed_forward: the network on x frozen per
+ * pixel by M [b,T,H*W]. */
+int ivf_i3d_stsearch(ivf_i3d_t* net, const float* x, int b, const int* target, float* raw, float* exp_avg,
+                     float* exp_avg_sq, const float* A_H, const float* A_W, int gh, int gw, float lam1, float lam2,
+                     float lam3, float lr, float beta1, float beta2, float eps, int N, int first_step, float* traj,
+                     void* ws, ivf_stream_t stream);
+int ivf_i3d_stperturbed_forward(ivf_i3d_t* net, const float* x, int b, const float* M, float* probs,
+                                ivf_stream_t stream);
+
 /* Scores of every one-blob candidate of b clips (see ivf_blob_count): scores [b,n] = probs[target[clip]] of the
  * perturbed clip under mode (0 freeze, 1 reverse).  Runs the grid in chunks of the plan's B rows (stage -> forward ->
  * pick), chunks crossing clip boundaries; one stream, no host sync, no allocation. */
@@ -485,6 +542,19 @@ int ivf_clstm_search(ivf_clstm_t* net, const float* x, int b, const int* target,
                      ivf_stream_t stream);
 int ivf_clstm_perturbed_forward(ivf_clstm_t* net, const float* x, int b, const float* mask, int mode,
                                 float* probs, ivf_stream_t stream);
+
+/* Spatio-temporal mask search (extension, see ivf_stmask_*): N iterations on raw [b,T,gh,gw] with per-pixel freeze
+ * through this plan; A_H [H,gh], A_W [W,gw] from ivf_stmask_axis_weights, on the device; traj [N,b,5] (optional) =
+ * (J, l1, tvt, tvs, score); ws = ivf_stsearch_workspace_bytes(b, T, H, W, gh, gw) bytes from the caller, 256-byte
+ * aligned.  One stream, no host synchronisation, no allocation.  _stperturbed_forward: the network on x frozen per
+ * pixel by M [b,T,H*W]. */
+int ivf_clstm_stsearch(ivf_clstm_t* net, const float* x, int b, const int* target, float* raw, float* exp_avg,
+                     float* exp_avg_sq, const float* A_H, const float* A_W, int gh, int gw, float lam1, float lam2,
+                     float lam3, float lr, float beta1, float beta2, float eps, int N, int first_step, float* traj,
+                     void* ws, ivf_stream_t stream);
+int ivf_clstm_stperturbed_forward(ivf_clstm_t* net, const float* x, int b, const float* M, float* probs,
+                                ivf_stream_t stream);
+
 /* ivf_i3d_blob_scores with the ConvLSTM backbone (candidates staged NCTHW). */
 int ivf_clstm_blob_scores(ivf_clstm_t* net, const float* x, int b, const int* target, int max_len, int mode,
                           float* scores, ivf_stream_t stream);

@@ -1297,6 +1297,27 @@ extern "C" int ivf_clstm_perturbed_forward(ivf_clstm_t* n, const float* x, int b
   return run_perturbed_forward(backbone(n), x, mask, b, mode, probs, (hipStream_t)stream);
 }
 
+// Spatio-temporal mask search (maskType 'spacetime', stmask_ops.hip): run_st_search on this plan; scratch from the caller.
+extern "C" int ivf_clstm_stsearch(ivf_clstm_t* net, const float* x, int b, const int* target, float* raw, float* exp_avg,
+                                float* exp_avg_sq, const float* A_H, const float* A_W, int gh, int gw, float lam1,
+                                float lam2, float lam3, float lr, float beta1, float beta2, float eps, int N,
+                                int first_step, float* traj, void* ws, ivf_stream_t stream) {
+  IVF_PROPAGATE(clstm_ready(net, b));
+  IVF_CHECK_ARG(x && target && raw && exp_avg && exp_avg_sq && A_H && A_W && ws, "clstm_stsearch: null pointer");
+  IVF_CHECK_ARG(N >= 0 && first_step >= 1, "clstm_stsearch: bad iteration counts");
+  IVF_CHECK_ARG(ivf_stsearch_workspace_bytes(b, net->cfg.T, net->cfg.H, net->cfg.W, gh, gw) > 0,
+                "clstm_stsearch: grid %dx%d outside 1..32 (or T > 64)", gh, gw);
+  return run_st_search(backbone(net), x, b, target, raw, exp_avg, exp_avg_sq, A_H, A_W, gh, gw, net->cfg.H, net->cfg.W,
+                       lam1, lam2, lam3, lr, beta1, beta2, eps, N, first_step, traj, ws, (hipStream_t)stream);
+}
+
+extern "C" int ivf_clstm_stperturbed_forward(ivf_clstm_t* net, const float* x, int b, const float* M, float* probs,
+                                           ivf_stream_t stream) {
+  IVF_PROPAGATE(clstm_ready(net, b));
+  IVF_CHECK_ARG(x && M, "clstm_stperturbed_forward: null pointer");
+  return run_st_perturbed_forward(backbone(net), x, M, b, probs, (hipStream_t)stream);
+}
+
 // Exhaustive one-blob search (maskType 'combi'), as ivf_i3d_blob_scores: candidates staged into the NCTHW buffer P.
 extern "C" int ivf_clstm_blob_scores(ivf_clstm_t* n, const float* x, int b, const int* target, int max_len, int mode,
                                      float* scores, ivf_stream_t stream) {

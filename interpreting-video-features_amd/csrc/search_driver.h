@@ -96,6 +96,68 @@ static int run_search(const Backbone& v, const float* x, int b, const int* targe
   return IVF_OK;
 }
 
+// ---------------------------------------------------------------- spatio-temporal masks (maskType 'spacetime')
+// An extension without a counterpart in the reference (stmask_ops.hip).  Its scratch belongs to the CALLER
+// (ivf_stsearch_workspace_bytes), so no plan's workspace size or carve order moves.
+struct StScratch {
+  size_t M = 0, dM = 0, sig = 0, dreg = 0, dsig = 0, terms = 0, score = 0;
+
+  // byte offsets of the pieces, each 256-byte aligned; returns the total
+  size_t carve(size_t B, size_t T, size_t HW, size_t cells) {
+    size_t top = 0;
+    auto take = [&top](size_t bytes) {
+      size_t off = top;
+      top += align_up(bytes, 256);
+      return off;
+    };
+    M = take(B * T * HW * 4);
+    dM = take(B * T * HW * 4);
+    sig = take(B * T * cells * 4);
+    dreg = take(B * T * cells * 4);
+    dsig = take(B * T * cells * 4);
+    terms = take(B * 3 * 4);
+    score = take(B * 4);
+    return top;
+  }
+};
+
+// x frozen per pixel by M [b,T,HW] (values in [0,1]) into the staged input, then the network
+static inline int run_st_perturbed_forward(const Backbone& v, const float* x, const float* M, int b, float* probs,
+                                           hipStream_t s) {
+  IVF_PROPAGATE(ivf_stfreeze_fwd(x, M, v.in, b, v.C, v.T, v.HW, v.layout, s));
+  return v.forward(v.plan, b, probs, s);
+}
+
+// N iterations of the spacetime loop on raw [b,T,gh,gw]: sigmoid + regulariser, expand to M, per-pixel freeze, network
+// forward and backward, dM, its adjoint expand, Adam.  traj rows [N,b,5] = (J, l1, tvt, tvs, score).  `ws`: the
+// caller's ivf_stsearch_workspace_bytes(b, T, H, W, gh, gw) bytes.  As run_search: one stream, no host
+// synchronisation, no allocation.
+static int run_st_search(const Backbone& v, const float* x, int b, const int* target, float* raw, float* exp_avg,
+                         float* exp_avg_sq, const float* A_H, const float* A_W, int gh, int gw, int H, int W, float lam1,
+                         float lam2, float lam3, float lr, float beta1, float beta2, float eps, int N, int first_step,
+                         float* traj, void* ws, hipStream_t s) {
+  StScratch c;
+  c.carve((size_t)b, (size_t)v.T, (size_t)v.HW, (size_t)gh * gw);
+  char* w = (char*)ws;
+  float *M = (float*)(w + c.M), *dM = (float*)(w + c.dM), *sig = (float*)(w + c.sig), *dreg = (float*)(w + c.dreg);
+  float *dsig = (float*)(w + c.dsig), *terms = (float*)(w + c.terms), *score = (float*)(w + c.score);
+  for (int it = 0; it < N; ++it) {
+    prof_set_iteration(it);
+    IVF_PROPAGATE(ivf_stmask_reg(raw, b, v.T, gh, gw, lam1, lam2, lam3, sig, terms, dreg, s));
+    IVF_PROPAGATE(ivf_stmask_expand_fwd(sig, A_H, A_W, M, b, v.T, gh, gw, H, W, s));
+    IVF_PROPAGATE(ivf_stfreeze_fwd(x, M, v.in, b, v.C, v.T, v.HW, v.layout, s));
+    IVF_PROPAGATE(v.forward(v.plan, b, nullptr, s));
+    IVF_PROPAGATE(v.backward(v.plan, b, target, score, s));
+    IVF_PROPAGATE(ivf_stfreeze_bwd(x, M, v.din, dM, b, v.C, v.T, v.HW, v.layout, s));
+    IVF_PROPAGATE(ivf_stmask_expand_bwd(dM, A_H, A_W, dsig, b, v.T, gh, gw, H, W, s));
+    IVF_PROPAGATE(ivf_stmask_step(raw, sig, dsig, dreg, terms, score, exp_avg, exp_avg_sq,
+                                  traj ? traj + (size_t)it * b * 5 : nullptr, b, v.T, gh, gw, first_step + it, lr, beta1,
+                                  beta2, eps, s));
+  }
+  prof_set_iteration(-1);
+  return IVF_OK;
+}
+
 // Exhaustive one-blob search (maskType 'combi'): the b*n candidates of b clips run in chunks of the plan's B rows --
 // stage straight into the input buffer, forward, pick the target score -- all on one stream, no host sync, no
 // allocation.  Chunks cross clip boundaries, so one clip still fills the plan.

@@ -178,6 +178,99 @@ class _Engine:
                                             L.stream()))
         return scores
 
+    # -------------------------------------------------------------- spatio-temporal masks (extension)
+    _has_st = True          # ivf_<prefix>_stsearch / _stperturbed_forward exist (not for the TF plan)
+
+    def _st_axes(self, grid, sigma):
+        """(gh, gw, sigma, A_H [H,gh], A_W [W,gw]) on the device: ivf_stmask_axis_weights, built once per (grid, sigma).
+        sigma None -> 0.5 * H / gh input pixels."""
+        if not self._has_st:
+            raise L.IvfError("spatio-temporal masks are built for the I3D and CLSTM plans only")
+        gh, gw = (int(v) for v in grid)
+        H, W = self.clip_shape[2:]
+        sigma = 0.5 * H / gh if sigma is None else float(sigma)
+        cache = self.__dict__.setdefault("_st_axis_cache", {})
+        key = (gh, gw, sigma)
+        if key not in cache:
+            mats = []
+            for n_out, n_in in ((H, gh), (W, gw)):
+                a = np.empty((n_out, max(n_in, 1)), dtype=np.float32)
+                L.check(L.lib().ivf_stmask_axis_weights(n_out, n_in, sigma, a.ctypes.data_as(c_void_p)))
+                mats.append(torch.from_numpy(a).to(self.device))
+            cache[key] = tuple(mats)
+        return (gh, gw, sigma) + cache[key]
+
+    def st_expand(self, S, grid, sigma=None):
+        """M [b,T,H,W] = A_H S A_W^T for S [b,T,gh,gw] in [0,1] (bilinear upsampling + Gaussian blur, one linear map)."""
+        gh, gw, _, AH, AW = self._st_axes(grid, sigma)
+        L.require_gpu(S)
+        S = L.f32c(S)
+        C, T, H, W = self.clip_shape
+        if S.dim() != 4 or tuple(S.shape[1:]) != (T, gh, gw):
+            raise L.IvfError(f"S must be [b,{T},{gh},{gw}], got {tuple(S.shape)}")
+        b = S.shape[0]
+        M = torch.empty(b, T, H, W, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().ivf_stmask_expand_fwd(L.ptr(S), L.ptr(AH), L.ptr(AW), L.ptr(M), b, T, gh, gw, H, W, L.stream()))
+        return M
+
+    def st_search(self, x, target, raw, lam1, lam2, N, grid, sigma=None, lam3=None, lr=0.2, betas=(0.9, 0.999), eps=1e-8,
+                  state=None, want_traj=True):
+        """N iterations of the spacetime loop on b clips: raw [b,T,gh,gw] is updated in place, the perturbation is the
+        per-pixel freeze by M = st_expand(sigmoid(raw)).  Returns (traj [N,b,5] = (J, l1, tvt, tvs, score), state);
+        lam3 (spatial TV) defaults to lam2."""
+        gh, gw, _, AH, AW = self._st_axes(grid, sigma)
+        x = self._clip(x)
+        b = x.shape[0]
+        C, T, H, W = self.clip_shape
+        tgt = self._targets(target, b)
+        L.require_gpu(raw)
+        if raw.dtype != torch.float32 or not raw.is_contiguous() or tuple(raw.shape) != (b, T, gh, gw):
+            raise L.IvfError(f"raw must be a contiguous float32 [b,{T},{gh},{gw}] tensor")
+        if state is None:
+            state = (torch.zeros_like(raw), torch.zeros_like(raw), 0)
+        m, v, done = state
+        nbytes = L.lib().ivf_stsearch_workspace_bytes(b, T, H, W, gh, gw)
+        if nbytes == 0:
+            raise L.IvfError(L.lib().ivf_last_error().decode())
+        ws = self.__dict__.get("_st_ws")
+        if ws is None or ws.numel() < nbytes:
+            with torch.cuda.device(self.device):
+                ws = self._st_ws = _arena(nbytes, self.device)
+        traj = torch.empty(N, b, 5, device=self.device) if want_traj else None
+        with torch.cuda.device(self.device):
+            L.check(self._fn("stsearch")(self._h, L.ptr(x), b, L.ptr(tgt), L.ptr(raw), L.ptr(m), L.ptr(v), L.ptr(AH),
+                                         L.ptr(AW), gh, gw, lam1, lam2, lam2 if lam3 is None else lam3, lr, betas[0],
+                                         betas[1], eps, int(N), done + 1, L.ptr(traj), L.ptr(ws), L.stream()))
+        return traj, (m, v, done + int(N))
+
+    def st_freeze(self, x, M):
+        """x [b,C,T,H,W] frozen per pixel by M [b,T,H,W] (values in [0,1]): the perturbed clips, NCTHW (ivf_stfreeze_fwd)."""
+        L.require_gpu(x)
+        x, M = L.f32c(x), L.f32c(M.to(x.device))
+        b, C, T, H, W = x.shape
+        if tuple(M.shape) != (b, T, H, W):
+            raise L.IvfError(f"M must be [b,{T},{H},{W}]")
+        p = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            L.check(L.lib().ivf_stfreeze_fwd(L.ptr(x), L.ptr(M), L.ptr(p), b, C, T, H * W, 0, L.stream()))
+        return p
+
+    def st_perturbed_forward(self, x, M):
+        """probs [b,K] of x frozen per pixel by M [b,T,H,W] (values in [0,1])."""
+        if not self._has_st:
+            raise L.IvfError("spatio-temporal masks are built for the I3D and CLSTM plans only")
+        x = self._clip(x)
+        b = x.shape[0]
+        C, T, H, W = self.clip_shape
+        M = L.f32c(M.to(self.device))
+        if tuple(M.shape) != (b, T, H, W):
+            raise L.IvfError(f"M must be [b,{T},{H},{W}]")
+        probs = torch.empty(b, self.K, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(self._fn("stperturbed_forward")(self._h, L.ptr(x), b, L.ptr(M), L.ptr(probs), L.stream()))
+        return probs
+
     def argmax(self, probs):
         b = probs.shape[0]
         t = torch.empty(b, dtype=torch.int32, device=self.device)
@@ -441,6 +534,7 @@ class TFCLSTMEngine(_Engine):
     The plan perturbs by freezing only and has no one-blob entry (the inherited `blob_scores` finds no symbol)."""
     _prefix = "tfclstm"
     _has_mode = False
+    _has_st = False
 
     def __init__(self, num_classes, clip_shape, units=(32, 32), kernel=(3, 5), stride=2, padding="valid",
                  recurrent_activation="hard_sigmoid", only_last_element_for_fc=True, max_batch=1, device=None):

@@ -46,8 +46,12 @@ def _unwrap(model):
 def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMaskType="freeze", classOI=None,
                     verbose=True, doGradCam=False, runTempMask=True, flavour="smth", sub_dir="run0",
                     results_path="results/", gradcam_size=None, write_files=True, device=None, visualise=True,
-                    mask_mode="central", max_mask_length=None, blob_batch=32):
-    """mask_mode 'combi' (the drivers' maskType='combi', smth:137-141) replaces init_mask + Adam by the exhaustive
+                    mask_mode="central", max_mask_length=None, blob_batch=32, mask_grid=None, mask_sigma=None, lam3=None):
+    """mask_mode 'spacetime' (the drivers' maskType='spacetime', an extension: DESIGN 11) searches a mask per frame
+    and grid cell (mask_grid, mask_sigma, lam3: see ivf_search.MaskSearch); its records also carry st_mask
+    [T,gh,gw], the heat-map strips blend the expanded mask where they blend the Grad-CAM map otherwise, and the KTH
+    flavour's perturbed-frame PNGs show the per-pixel freeze that was searched (the mark in their corner is time_mask).
+    mask_mode 'combi' (the drivers' maskType='combi', smth:137-141) replaces init_mask + Adam by the exhaustive
     one-blob search over masks of length <= max_mask_length; its plan holds at least blob_batch clips so that the
     candidates of a loader batch fill it.  Its records also carry blob_start, blob_length and blob_scores."""
     net = _unwrap(model)
@@ -76,9 +80,14 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                        grad_cam_type=hyper_params.get("gradCamType", "guessed"),
                                        do_gradcam=doGradCam, run_temp_mask=runTempMask,
                                        normalize_per_frame=True, gradcam_size=gradcam_size, mask_mode=mask_mode,
-                                       max_mask_length=max_mask_length)
+                                       max_mask_length=max_mask_length, mask_grid=mask_grid, mask_sigma=mask_sigma,
+                                       lam3=lam3)
         res = search.run(xs, labels[keep])
         host = {k: v.detach().cpu() for k, v in res.items() if k != "gradcam"}
+        spacetime = runTempMask and mask_mode == "spacetime"
+        st_maps = eng.st_expand(res["st_mask"], search.st_grid(xs), mask_sigma) if spacetime and write_files and visualise \
+            else None
+        st_pert = eng.st_freeze(xs, st_maps) if st_maps is not None and flavour != "smth" else None   # what was searched
         if doGradCam:
             host["gradcam"] = res["gradcam"].detach().cpu()
         for j, bi in enumerate(keep):
@@ -106,6 +115,8 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                 if mask_mode == "combi":
                     time_results[-1].update(blob_start=int(host["blob"][j, 0]), blob_length=int(host["blob"][j, 1]),
                                             blob_scores=host["blob_scores"][j].numpy())
+                if spacetime:
+                    time_results[-1].update(st_mask=host["st_mask"][j].numpy())
                 tmask = res["time_mask"][j].clone()     # the clip's own [T] tensor, as the reference's time_mask
                 if verbose:
                     print("resulting mask is: ", tmask)
@@ -118,13 +129,14 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                 # types (the dot row snaps a host copy: `tmask` keeps its sigmoid values, as the reference's
                 # CUDA time_mask does), then for KTH the perturbed frames as PNGs of the SOFT mask
                 import visualisation as viz
-                if doGradCam:
+                if doGradCam or st_maps is not None:
+                    heat = st_maps[j] if st_maps is not None else res["gradcam"][j]
                     for kind in ("freeze", "reverse"):
-                        viz.create_image_arrays(xs, res["gradcam"][j], tmask, j, kind, d, str(vid), 0,
-                                                xs.shape[4], xs.shape[3])
+                        viz.create_image_arrays(xs, heat, tmask, j, kind, d, str(vid), 0, xs.shape[4], xs.shape[3])
                 if flavour != "smth":
                     import mask as _mask
-                    viz.vizualize_results(xs[j], _mask.perturb_sequence(xs, tmask, temporalMaskType)[j], tmask,
+                    pert = st_pert[j] if st_pert is not None else _mask.perturb_sequence(xs, tmask, temporalMaskType)[j]
+                    viz.vizualize_results(xs[j], pert, tmask,
                                           rootDir=d, case=str(vid), markImgs=True, iterTest=False)
             # smth:303 appends only when both Grad-CAM and the mask search ran; KTH:367 whenever the search ran
             if runTempMask and (doGradCam or flavour != "smth"):

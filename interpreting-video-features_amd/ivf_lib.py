@@ -85,6 +85,15 @@ _SIGS = {
     "ivf_blob_count": (c_int, [_I, _I]),
     "ivf_blob_stage": (c_int, [_P, _I, _I, _I, _I, _I, _I, ctypes.c_longlong, _I, _P, _I, _P]),
     "ivf_blob_select": (c_int, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P]),
+    # csrc/stmask_ops.hip (maskType 'spacetime', documented extension)
+    "ivf_stmask_axis_weights": (c_int, [_I, _I, _F, _P]),
+    "ivf_stmask_expand_fwd": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "ivf_stmask_expand_bwd": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "ivf_stfreeze_fwd": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ivf_stfreeze_bwd": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ivf_stmask_reg": (c_int, [_P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P]),
+    "ivf_stmask_step": (c_int, [_P] * 9 + [_I] * 5 + [_F] * 4 + [_P]),
+    "ivf_stsearch_workspace_bytes": (c_size_t, [_I] * 6),
     "ivf_clip_ingest_u8": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ivf_conv3d": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
     "ivf_bn_fold": (c_int, [_P, _P, _P, _P, _F, _P, _P, _I, _P]),
@@ -123,6 +132,8 @@ _SIGS = {
     "ivf_i3d_act_elem_bytes": (c_int, [_P]),
     "ivf_i3d_search": (c_int, [_P, _P, _I, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _I, _I, _I, _P, _P]),
     "ivf_i3d_perturbed_forward": (c_int, [_P, _P, _I, _P, _I, _P, _P]),
+    "ivf_i3d_stsearch": (c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I] + [_F] * 7 + [_I, _I, _P, _P, _P]),
+    "ivf_i3d_stperturbed_forward": (c_int, [_P, _P, _I, _P, _P, _P]),
     "ivf_i3d_blob_scores": (c_int, [_P, _P, _I, _P, _I, _I, _P, _P]),
     "ivf_i3d_gradcam": (c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "ivf_i3d_gradcam_layer": (c_int, [_P, _P, _I, _P, c_char_p, _I, _I, _I, _P, _P, _P]),
@@ -156,6 +167,8 @@ _SIGS = {
     "ivf_clstm_backward": (c_int, [_P, _I, _P, _P, _P, _P, _P]),
     "ivf_clstm_search": (c_int, [_P, _P, _I, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _I, _I, _I, _P, _P]),
     "ivf_clstm_perturbed_forward": (c_int, [_P, _P, _I, _P, _I, _P, _P]),
+    "ivf_clstm_stsearch": (c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I] + [_F] * 7 + [_I, _I, _P, _P, _P]),
+    "ivf_clstm_stperturbed_forward": (c_int, [_P, _P, _I, _P, _P, _P]),
     "ivf_clstm_blob_scores": (c_int, [_P, _P, _I, _P, _I, _I, _P, _P]),
     "ivf_clstm_gradcam_reduce": (c_int, [_P, _P, POINTER(c_int), _I, _P, _P, _I, _I, _I, _I, _P]),
     "ivf_clstm_set_cam_steps": (c_int, [_P, POINTER(c_int), _I]),

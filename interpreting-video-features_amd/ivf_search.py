@@ -133,12 +133,20 @@ def blob_masks(best, T):
 class MaskSearch:
     def __init__(self, engine, lam1=0.01, lam2=0.02, n_iter=300, mask_type="freeze", threshold=0.9,
                  lr=0.2, grad_cam_type="guessed", do_gradcam=True, run_temp_mask=True,
-                 normalize_per_frame=True, gradcam_size=None, mask_mode="central", max_mask_length=None):
+                 normalize_per_frame=True, gradcam_size=None, mask_mode="central", max_mask_length=None,
+                 mask_grid=None, mask_sigma=None, lam3=None):
         """mask_mode 'central': init_mask('central') + n_iter Adam steps (smth:188-214); 'combi': the exhaustive
-        one-blob search (smth:137-141) over masks of length <= max_mask_length (default T), no gradient descent."""
-        if mask_mode not in ("central", "combi"):
-            raise L.IvfError(f"mask_mode must be 'central' or 'combi', got {mask_mode!r}")
+        one-blob search (smth:137-141) over masks of length <= max_mask_length (default T), no gradient descent;
+        'spacetime' (an extension without a counterpart in the reference): the gradient search on a mask per
+        frame and grid cell -- mask_grid (gh, gw) (default one cell per 32 input pixels: 7x7 at 224^2, 4x5 at
+        120x160), mask_sigma the blur in input pixels (default 0.5 H / gh), lam3 the spatial TV weight (default lam2);
+        the perturbation is the per-pixel freeze."""
+        if mask_mode not in ("central", "combi", "spacetime"):
+            raise L.IvfError(f"mask_mode must be 'central', 'combi' or 'spacetime', got {mask_mode!r}")
+        if mask_mode == "spacetime" and mask_type != "freeze":
+            raise L.IvfError("mask_mode 'spacetime' perturbs by freezing only")
         self.mask_mode, self.max_mask_length = mask_mode, max_mask_length
+        self.mask_grid, self.mask_sigma, self.lam3 = mask_grid, mask_sigma, lam3
         self.engine = engine
         self.lam1, self.lam2, self.n_iter = float(lam1), float(lam2), int(n_iter)
         self.mask_type, self.threshold, self.lr = mask_type, threshold, lr
@@ -165,6 +173,8 @@ class MaskSearch:
         out["original_score_true"] = probs[idx, labels.long()]
         if self.run_temp_mask and self.mask_mode == "combi":
             self._run_combi(x, target, probs, out)
+        elif self.run_temp_mask and self.mask_mode == "spacetime":
+            self._run_spacetime(x, target, probs, out, want_traj)
         elif self.run_temp_mask:
             raw, info = init_masks_central(eng, x, target, probs[idx, target.long()], self.threshold,
                                            self.mask_type)                   # smth:188-190
@@ -212,6 +222,43 @@ class MaskSearch:
         out["blob_objective"] = sel["objective"]
         out["blob_minimal"] = sel["minimal"]
         out["blob_scores"] = scores
+
+
+    def st_grid(self, x):
+        if self.mask_grid is not None:
+            return tuple(int(v) for v in self.mask_grid)
+        return max(1, round(x.shape[3] / 32)), max(1, round(x.shape[4] / 32))
+
+    def _run_spacetime(self, x, target, probs, out, want_traj):
+        """maskType 'spacetime': init_mask('central') rows broadcast over the grid, n_iter iterations of the spacetime
+        loop; st_mask = sigmoid(raw) [b,T,gh,gw], time_mask = its spatial mean per frame, and from time_mask the
+        reverse score, ranking and snapped mask with the code of the temporal search."""
+        eng = self.engine
+        b, T = x.shape[0], x.shape[2]
+        dev = x.device
+        idx = torch.arange(b, device=dev)
+        gh, gw = self.st_grid(x)
+        rows, info = init_masks_central(eng, x, target, probs[idx, target.long()], self.threshold, "freeze")
+        out["init_mask"] = rows.clone()
+        raw = rows.view(b, T, 1, 1).expand(b, T, gh, gw).contiguous()
+        traj, _ = eng.st_search(x, target, raw, self.lam1, self.lam2, self.n_iter, (gh, gw), self.mask_sigma,
+                                lam3=self.lam3, lr=self.lr, want_traj=True)
+        S = torch.empty_like(raw)
+        mean = torch.empty(b, T, device=dev)
+        ah, aw = torch.full((1, gh), 1.0 / gh, device=dev), torch.full((1, gw), 1.0 / gw, device=dev)
+        with torch.cuda.device(dev):
+            L.check(L.lib().ivf_sigmoid(L.ptr(raw), L.ptr(S), raw.numel(), L.stream()))
+            # the spatial mean per frame = the expand onto a single pixel (H = W = 1) with the uniform rows 1/gh, 1/gw
+            # as its two matrices: the same fixed-order sums as everywhere else, no new kernel (see ivf_hip.h)
+            L.check(L.lib().ivf_stmask_expand_fwd(L.ptr(S), L.ptr(ah), L.ptr(aw), L.ptr(mean), b, T, gh, gw, 1, 1, L.stream()))
+        out["st_mask"] = S
+        out["time_mask"] = mean
+        out["freeze_score"] = traj[-1, :, 4] if self.n_iter > 0 else torch.full((b,), float("nan"), device=dev)
+        out["reverse_score"] = eng.perturbed_forward(x, mean, "reverse")[idx, target.long()]
+        out["ranking"] = frame_ranking(mean)
+        out["snapped"] = mean > 0.5
+        if want_traj:
+            out["traj"] = traj
 
 
 RECORD_INT_FIELDS = ("clip_id", "pred_class", "target")
