@@ -184,6 +184,38 @@ int ivf_stmask_step(float* raw, const float* sig, const float* dscore_dsig, cons
  * 0 with the message set for a shape the loop refuses. */
 size_t ivf_stsearch_workspace_bytes(int B, int T, int H, int W, int gh, int gw);
 
+/* ------------------------------------------------------------------ exhaustive one-box search (maskType 'stcombi')
+ * The gradient-free counterpart of 'spacetime', as 'combi' is of the temporal gradient search; an extension as well.
+ * A candidate (a, L, i0, bh, j0, bw) is the binary S that is 1 on frames [a, a+L), grid rows [i0, i0+bh) and grid
+ * columns [j0, j0+bw): one temporal blob times one rectangle of cells, L <= max_len, bh <= mh, bw <= mw.  The three axes
+ * are three one-blob tables in the order of ivf_blob_count (length ascending, then start);
+ * k = (kt n_h + kh) n_w + kw, n = n_t n_h n_w with n_t = ivf_blob_count(T, max_len), n_h = ivf_blob_count(gh, mh),
+ * n_w = ivf_blob_count(gw, mw).
+ * ivf_box_count: HOST.  n, or -1 (message set) unless 1 <= max_len <= T <= 64, 1 <= mh <= gh <= 32,
+ * 1 <= mw <= gw <= 32. */
+long long ivf_box_count(int T, int max_len, int gh, int gw, int mh, int mw);
+/* Rows [first, first+count) of the flattened (clip, candidate) list of b clips x [b,C,T,H,W] into p; row j is clip
+ * (first+j)/n, candidate (first+j)%n; count <= 65535.  out_cpad as ivf_blob_stage: 0 NCTHW [count,C,T,HW], 4 16-byte
+ * channels-last pixels [count,T,HW,4] (C <= 4, pad lanes +0.0).  A_H [H,gh], A_W [W,gw] on the device.  The rows equal
+ * (==) what ivf_stmask_expand_fwd followed by ivf_stfreeze_fwd write for the candidate's binary S; neither S nor M is
+ * ever in memory. */
+int ivf_box_stage(const float* x, int b, int C, int T, int H, int W, const float* A_H, const float* A_W, int gh, int gw,
+                  int max_len, int mh, int mw, long long first, int count, float* p, int out_cpad, ivf_stream_t stream);
+/* Selection over a score grid scores [b,n], one workgroup per clip.
+ * J_k = (lam1 L bh bw + lam2 TVt_k + lam3 TVs_k) / (gh gw) + s_k, TVt and TVs those of ivf_stmask_reg on the binary S
+ * (closed form; the same fp32 expressions and order as the spacetime loop's trajectory row).  best [b,6] =
+ * (a, L, i0, bh, j0, bw) of argmin J (NaN skipped, the smaller k on a tie, all -1 if every score is NaN); best_obj [b]
+ * and obj [b,n] optional; minimal [b,6] (optional): the smallest volume L bh bw with some
+ * r = (orig - s) / (orig - full) >= threshold, the largest r within it, then the smaller k; all -1 if none. */
+int ivf_box_select(const float* scores, const float* orig, const float* full, int b, int T, int gh, int gw, int max_len,
+                   int mh, int mw, float lam1, float lam2, float lam3, float threshold, int* best, float* best_obj,
+                   float* obj, int* minimal, ivf_stream_t stream);
+/* Occlusion map from the score grid: drop [b,T,gh,gw], drop[b,t,i,j] = mean of (orig[b] - s_k) over the candidates
+ * whose box covers cell (t,i,j), summed in ascending k; NaN scores are neither summed nor counted (NaN where none is
+ * left).  One thread per cell, which visits the covering candidates only. */
+int ivf_box_drop(const float* scores, const float* orig, int b, int T, int gh, int gw, int max_len, int mh, int mw,
+                 float* drop, ivf_stream_t stream);
+
 /* Clip ingest: the arithmetic of ImLoader.__getitem__ /
  * KTHImLoader.__getitem__ after the JPEG decode (data_loader_jpg.py:29-37,
  * data_loader_kth.py:25-44): uint8 frames [B][T][H][W][C] -> float32 (exact), permuted to
@@ -474,6 +506,11 @@ int ivf_i3d_stperturbed_forward(ivf_i3d_t* net, const float* x, int b, const flo
  * pick), chunks crossing clip boundaries; one stream, no host sync, no allocation. */
 int ivf_i3d_blob_scores(ivf_i3d_t* net, const float* x, int b, const int* target, int max_len, int mode,
                         float* scores, ivf_stream_t stream);
+/* Scores of every one-box candidate of b clips (see ivf_box_count): scores [b,n] = probs[target[clip]] of the clip
+ * frozen per pixel by the candidate's expanded mask, in chunks of the plan's B rows (ivf_box_stage -> forward); b may
+ * exceed B.  One stream, no host synchronisation, no allocation. */
+int ivf_i3d_box_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W, int gh,
+                      int gw, int max_len, int mh, int mw, float* scores, ivf_stream_t stream);
 
 /* GradCamVideo.__call__ for archType "I3D" / target layer Mixed_5c,
  * grad_cam_videos.py:64-142, for b clips.  target[b] (device) selects the class;
@@ -558,6 +595,11 @@ int ivf_clstm_stperturbed_forward(ivf_clstm_t* net, const float* x, int b, const
 /* ivf_i3d_blob_scores with the ConvLSTM backbone (candidates staged NCTHW). */
 int ivf_clstm_blob_scores(ivf_clstm_t* net, const float* x, int b, const int* target, int max_len, int mode,
                           float* scores, ivf_stream_t stream);
+/* Scores of every one-box candidate of b clips (see ivf_box_count): scores [b,n] = probs[target[clip]] of the clip
+ * frozen per pixel by the candidate's expanded mask, in chunks of the plan's B rows (ivf_box_stage -> forward); b may
+ * exceed B.  One stream, no host synchronisation, no allocation. */
+int ivf_clstm_box_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W, int gh,
+                      int gw, int max_len, int mh, int mw, float* scores, ivf_stream_t stream);
 
 /* Grad-CAM on the ConvLSTM's pooled layer outputs, stored [B,T,hid,plane] (plane = Hp*Wp), fp32:
  * weights[b,c] = mean over (selected steps, plane) of grad (grad_cam_videos.py:98), cam[b,e,:] =

@@ -23,18 +23,22 @@ _state = {"sub_dir": "run0"}
 
 def find_masks(dat_loader, model, hyper_params, lam1, lam2, N, maskType="gradient", temporalMaskType="freeze",
                classOI=None, verbose=True, maxMaskLength=None, doGradCam=False, runTempMask=True, maskGrid=None,
-               maskSigma=None, lam3=None):
+               maskSigma=None, lam3=None, maxBox=None):
     """smth:125-315.  maskType 'combi' runs the exhaustive one-blob search over masks of length <= maxMaskLength
     (smth:137-141, no gradient descent; N is unused); any other maskType keeps the gradient search from
     init_mask(mode="central"), which the reference hard-codes (smth:190).  maskType 'spacetime' (an extension, no
     counterpart in the reference) searches a mask per frame and cell of a maskGrid (gh, gw) grid, blurred by maskSigma
-    input pixels, with lam3 on the spatial TV term; records also carry 'st_mask' [T,gh,gw]."""
+    input pixels, with lam3 on the spatial TV term; records also carry 'st_mask' [T,gh,gw].  maskType 'stcombi' (an
+    extension as well) is the exhaustive counterpart of 'spacetime': every box of one temporal blob (length <=
+    maxMaskLength, default T) times one rectangle of at most maxBox = (mh, mw) grid cells (default the whole grid) is
+    scored and the minimiser of the spacetime loss kept; N is unused; records also carry 'st_mask' (binary),
+    'box_start', 'box_length', 'box_rows', 'box_cols' and 'box_drop'."""
     return ivf_find_masks.find_masks_impl(
         dat_loader, model, hyper_params, lam1, lam2, N, temporalMaskType, classOI, verbose, doGradCam,
         runTempMask, flavour="smth", sub_dir=_state["sub_dir"],
         gradcam_size=(RESIZE_SIZE_HEIGHT, RESIZE_SIZE_WIDTH),
-        mask_mode=maskType if maskType in ("combi", "spacetime") else "central", max_mask_length=maxMaskLength,
-        mask_grid=maskGrid, mask_sigma=maskSigma, lam3=lam3)
+        mask_mode=maskType if maskType in ("combi", "spacetime", "stcombi") else "central",
+        max_mask_length=maxMaskLength, mask_grid=maskGrid, mask_sigma=maskSigma, lam3=lam3, max_box=maxBox)
 
 
 def main(argv=None):

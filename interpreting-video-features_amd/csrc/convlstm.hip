@@ -1328,6 +1328,17 @@ extern "C" int ivf_clstm_blob_scores(ivf_clstm_t* n, const float* x, int b, cons
   return run_blob_scores(backbone(n), x, b, target, max_len, mode, scores, (hipStream_t)stream);
 }
 
+// Exhaustive one-box search (maskType 'stcombi'): run_box_scores, candidates staged straight into the input buffer.
+extern "C" int ivf_clstm_box_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H,
+                                   const float* A_W, int gh, int gw, int max_len, int mh, int mw, float* scores,
+                                   ivf_stream_t stream) {
+  IVF_PROPAGATE(clstm_ready(net, 1));
+  IVF_CHECK_ARG(x && target && A_H && A_W && scores, "clstm_box_scores: null pointer");
+  IVF_CHECK_ARG(b > 0, "clstm_box_scores: bad batch %d", b);
+  return run_box_scores(backbone(net), x, b, target, A_H, A_W, gh, gw, net->cfg.H, net->cfg.W, max_len, mh, mw, scores,
+                        (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- Grad-CAM (grad_cam_videos.py:64-142, archType "CLSTM")
 
 static int cam_steps_from(const int* steps, int n_steps, int T, CamSteps* st) {

@@ -883,6 +883,17 @@ extern "C" int ivf_i3d_blob_scores(ivf_i3d_t* net, const float* x, int b, const 
   return run_blob_scores(backbone(net), x, b, target, max_len, mode, scores, (hipStream_t)stream);
 }
 
+// Exhaustive one-box search (maskType 'stcombi'): run_box_scores, candidates staged straight into the input buffer.
+extern "C" int ivf_i3d_box_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H,
+                                   const float* A_W, int gh, int gw, int max_len, int mh, int mw, float* scores,
+                                   ivf_stream_t stream) {
+  IVF_PROPAGATE(check_ready(net, 1));
+  IVF_CHECK_ARG(x && target && A_H && A_W && scores, "i3d_box_scores: null pointer");
+  IVF_CHECK_ARG(b > 0, "i3d_box_scores: bad batch %d", b);
+  return run_box_scores(backbone(net), x, b, target, A_H, A_W, gh, gw, net->cfg.H, net->cfg.W, max_len, mh, mw, scores,
+                        (hipStream_t)stream);
+}
+
 extern "C" int ivf_i3d_gradcam(ivf_i3d_t* net, const float* x, int b, const int* target, int per_frame,
                                int out_h, int out_w, float* cam, float* probs, ivf_stream_t stream) {
   IVF_PROPAGATE(check_ready(net, b));

@@ -23,6 +23,18 @@ void prof_name(int variant, const char* fmt, ...);   // kernel name of a profile
 int blob_pick(const float* probs, const int* target, int K, int n, long long first, int count, float* scores,
               hipStream_t s);
 
+// index k of the canonical one-blob order (length ascending, then start) on an axis of T positions -> (start, length);
+// the three axes of the one-box search (stmask_ops.hip) decode with it as well
+__device__ __forceinline__ void blob_decode(int k, int T, int* a, int* L) {
+  int l = 1;
+  while (k >= T - l + 1) {
+    k -= T - l + 1;
+    ++l;
+  }
+  *a = k;
+  *L = l;
+}
+
 // classification head and Grad-CAM reduction (pool_head.hip) on activations / gradients stored as fp32, or as bf16 when
 // `bf16` is set: what ivf_head_fwd{,_bf16}, ivf_head_bwd{,_bf16} and ivf_gradcam_reduce{,_bf16} do, storage type at run time
 int head_fwd(const void* feat, bool bf16, const float* w, const float* bias, float* pooled, float* logits, float* probs,

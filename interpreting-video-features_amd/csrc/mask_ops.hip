@@ -846,16 +846,6 @@ extern "C" int ivf_sigmoid(const float* x, float* y, int n, ivf_stream_t stream)
 // clip into the network's staged-input buffer; the K copies never exist in NCTHW.
 namespace ivf {
 
-__device__ __forceinline__ void blob_decode(int k, int T, int* a, int* L) {
-  int l = 1;
-  while (k >= T - l + 1) {
-    k -= T - l + 1;
-    ++l;
-  }
-  *a = k;
-  *L = l;
-}
-
 __device__ __forceinline__ int blob_src(int u, int a, int L, int mode) {
   if (u < a || u >= a + L) return u;
   return mode == 0 ? (a > 0 ? a - 1 : 0) : 2 * a + L - 1 - u;

@@ -175,4 +175,22 @@ static inline int run_blob_scores(const Backbone& v, const float* x, int b, cons
   return IVF_OK;
 }
 
+// Exhaustive one-box search (maskType 'stcombi', stmask_ops.hip): run_blob_scores with the box staging -- the b*n
+// candidates in chunks of the plan's B rows across clip boundaries, ivf_box_stage -> forward -> blob_pick, one stream,
+// no host synchronisation, no allocation.
+static inline int run_box_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,
+                                 const float* A_W, int gh, int gw, int H, int W, int max_len, int mh, int mw,
+                                 float* scores, hipStream_t s) {
+  const long long n = ivf_box_count(v.T, max_len, gh, gw, mh, mw);
+  if (n < 0) return IVF_ERR_BAD_ARG;
+  const long long total = (long long)b * n;
+  for (long long first = 0; first < total; first += v.B) {
+    const int cnt = (int)std::min<long long>(v.B, total - first);
+    IVF_PROPAGATE(ivf_box_stage(x, b, v.C, v.T, H, W, A_H, A_W, gh, gw, max_len, mh, mw, first, cnt, v.in, v.layout, s));
+    IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
+    IVF_PROPAGATE(blob_pick(v.probs, target, v.K, (int)n, first, cnt, scores, s));
+  }
+  return IVF_OK;
+}
+
 }  // namespace ivf

@@ -421,7 +421,243 @@ __global__ __launch_bounds__(256) void stmask_step_kernel(float* __restrict__ ra
   }
 }
 
+// ---------------------------------------------------------------- one-box exhaustive search (maskType 'stcombi')
+// The gradient-free counterpart of the spacetime search (as 'combi' is of 'central'): every candidate is one temporal
+// blob [a, a+L) times one rectangle of grid cells, rows [i0, i0+bh) x columns [j0, j0+bw).  The three axes are three
+// one-blob tables in the canonical order of ivf_blob_count; k = (kt n_h + kh) n_w + kw.
+//
+// Staging writes what ivf_stmask_expand_fwd + ivf_stfreeze_fwd write for the candidate's binary S, without S or M in
+// memory.  With S in {0, 1} the expand's sums lose their zero terms exactly (x + 0 * a == x for the finite,
+// non-negative values involved; 1 * a == a), so
+//   rw[x]   = sum_{j in columns, ascending} A_W[x,j]
+//   M[y,x]  = sum_{i in rows, ascending} A_H[y,i] * rw[x]      on the blob's frames, 0 on the others,
+// every partial sum rounded as stmask_expand_fwd_kernel rounds it (this file is built without contraction: a multiply
+// and an add each).  The recurrence is stfreeze_fwd's expression with that M; on a frame with M = 0 it returns X[u].
+struct BoxAxes {
+  int T, gh, gw, n_h, n_w, n;
+};
+
+struct Box {
+  int clip, a, L, i0, bh, j0, bw;
+};
+
+__device__ __forceinline__ Box box_decode(long long g, const BoxAxes& ax) {
+  Box c;
+  c.clip = (int)(g / ax.n);
+  const int k = (int)(g % ax.n);
+  const int kw = k % ax.n_w, kh = (k / ax.n_w) % ax.n_h, kt = k / (ax.n_w * ax.n_h);
+  blob_decode(kt, ax.T, &c.a, &c.L);
+  blob_decode(kh, ax.gh, &c.i0, &c.bh);
+  blob_decode(kw, ax.gw, &c.j0, &c.bw);
+  return c;
+}
+
+// M[y,x] of the box on one of its frames; A_H row y and A_W row x are read through the cache (a workgroup shares its
+// candidate, a wave mostly its row y)
+__device__ __forceinline__ float box_mask_at(const float* __restrict__ AH, const float* __restrict__ AW, int gh, int gw,
+                                             int y, int x, const Box& c) {
+  float rw = 0.f;
+  for (int j = c.j0; j < c.j0 + c.bw; ++j) rw += AW[(size_t)x * gw + j];
+  float m = 0.f;
+  for (int i = c.i0; i < c.i0 + c.bh; ++i) m += AH[(size_t)y * gh + i] * rw;
+  return m;
+}
+
+// 16-byte channels-last pixels (C <= 4): one thread per pixel of row blockIdx.y, as stfreeze_fwd_cl4_kernel.  With TT > 0
+// (T == TT) the 16 frames of a piece are requested before the scan goes over them.
+template <int TT>   // 0, or a multiple of 16
+__global__ __launch_bounds__(256) void box_stage_cl4_kernel(const float* __restrict__ x, const float* __restrict__ AH,
+                                                            const float* __restrict__ AW, float* __restrict__ p, int C,
+                                                            int W, int HW, BoxAxes ax, long long first) {
+  const int px = blockIdx.x * 256 + threadIdx.x;
+  if (px >= HW) return;
+  const int row = blockIdx.y, T = TT > 0 ? TT : ax.T;
+  const Box c = box_decode(first + row, ax);
+  const float mb = box_mask_at(AH, AW, ax.gh, ax.gw, px / W, px % W, c);
+  const float* xc = x + (size_t)c.clip * C * T * HW + px;
+  float* pr = p + ((size_t)row * T * HW + px) * 4;
+  float prev[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (TT > 0) {
+#pragma unroll 1
+    for (int u0 = 0; u0 < TT; u0 += 16) {
+      float xv[4][16];
+#pragma unroll
+      for (int ch = 0; ch < 4; ++ch)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          xv[ch][j] = 0.f;
+          if (ch < C) xv[ch][j] = xc[((size_t)ch * TT + u0 + j) * HW];
+        }
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int u = u0 + j;
+        const float m = (u >= c.a && u < c.a + c.L) ? mb : 0.f;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch)
+          if (ch < C) {
+            v[ch] = u ? (1.f - m) * xv[ch][j] + m * prev[ch] : xv[ch][j];
+            prev[ch] = v[ch];
+          }
+        *reinterpret_cast<float4*>(pr + (size_t)u * HW * 4) = make_float4(v[0], v[1], v[2], v[3]);
+      }
+    }
+  } else {
+    for (int u = 0; u < T; ++u) {
+      const float m = (u >= c.a && u < c.a + c.L) ? mb : 0.f;
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+      for (int ch = 0; ch < C; ++ch) {
+        float xv = xc[((size_t)ch * T + u) * HW];
+        v[ch] = u ? (1.f - m) * xv + m * prev[ch] : xv;
+        prev[ch] = v[ch];
+      }
+      *reinterpret_cast<float4*>(pr + (size_t)u * HW * 4) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+  }
+}
+
+// NCTHW: one thread per pixel of row blockIdx.y, channel after channel (the mask value is the pixel's, not the channel's)
+__global__ __launch_bounds__(256) void box_stage_ncthw_kernel(const float* __restrict__ x, const float* __restrict__ AH,
+                                                              const float* __restrict__ AW, float* __restrict__ p, int C,
+                                                              int W, int HW, BoxAxes ax, long long first) {
+  const int px = blockIdx.x * 256 + threadIdx.x;
+  if (px >= HW) return;
+  const int row = blockIdx.y, T = ax.T;
+  const Box c = box_decode(first + row, ax);
+  const float mb = box_mask_at(AH, AW, ax.gh, ax.gw, px / W, px % W, c);
+  for (int ch = 0; ch < C; ++ch) {
+    const float* xp = x + ((size_t)(c.clip * C + ch) * T) * HW + px;
+    float* pp = p + ((size_t)(row * C + ch) * T) * HW + px;
+    float prev = 0.f;
+    for (int u = 0; u < T; ++u) {
+      const float m = (u >= c.a && u < c.a + c.L) ? mb : 0.f;
+      float xv = xp[(size_t)u * HW];
+      float v = u ? (1.f - m) * xv + m * prev : xv;
+      prev = v;
+      pp[(size_t)u * HW] = v;
+    }
+  }
+}
+
+// The regulariser of stmask_reg_kernel on the binary S of a box, in closed form (small integers, exact in fp32):
+//   sum S = L bh bw;  TVt = bh bw (w(a-1) [a >= 1] + w(a+L-1) [a+L < T]), w the pair weights of stmask_reg_kernel
+//   (interior pairs count twice; nothing at T < 3);  TVs = L (bw ([i0 >= 1] + [i0+bh < gh]) + bh ([j0 >= 1] + [j0+bw < gw])).
+// J = l1 + tvt + tvs + score with each term (lam * sum) / cells: the expressions and the order of stmask_reg_kernel's
+// terms and stmask_step_kernel's trajectory row.
+__device__ __forceinline__ float box_objective(const Box& c, int T, int gh, int gw, float lam1, float lam2, float lam3,
+                                               float score) {
+  const float fc = (float)(gh * gw);
+  const int vol = c.L * c.bh * c.bw;
+  int wt = 0;
+  if (T >= 3) {
+    if (c.a >= 1) wt += (c.a - 1 <= T - 3 ? 1 : 0) + (c.a - 1 >= 1 ? 1 : 0);
+    if (c.a + c.L < T) wt += (c.a + c.L - 1 <= T - 3 ? 1 : 0) + (c.a + c.L - 1 >= 1 ? 1 : 0);
+  }
+  const int tvt = c.bh * c.bw * wt;
+  const int tvs = c.L * (c.bw * ((c.i0 >= 1) + (c.i0 + c.bh < gh)) + c.bh * ((c.j0 >= 1) + (c.j0 + c.bw < gw)));
+  const float l1 = (lam1 * (float)vol) / fc, t = (lam2 * (float)tvt) / fc, sp = (lam3 * (float)tvs) / fc;
+  return l1 + t + sp + score;
+}
+
+// Selection, one workgroup per clip: a thread walks k = tid, tid + 256, ... and keeps its own winners; thread 0 then
+// goes over the 256 in order.  best = argmin J (NaN skipped, the smaller k on a tie); minimal = the smallest volume
+// L bh bw with some r = (orig - s) / (orig - full) >= threshold, the largest r within it, then the smaller k.
+__global__ __launch_bounds__(256) void box_select_kernel(const float* __restrict__ scores, const float* __restrict__ orig,
+                                                         const float* __restrict__ full, BoxAxes ax, float lam1,
+                                                         float lam2, float lam3, float threshold, int* __restrict__ best,
+                                                         float* __restrict__ best_obj, float* __restrict__ obj,
+                                                         int* __restrict__ minimal) {
+  __shared__ float bj_s[256], mr_s[256];
+  __shared__ int bk_s[256], mk_s[256], mv_s[256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* s = scores + (size_t)b * ax.n;
+  const float o = orig[b], den = o - full[b];
+  int bk = -1, mk = -1, mv = 0;
+  float bj = 0.f, mr = 0.f;
+  for (int k = tid; k < ax.n; k += 256) {
+    const Box c = box_decode(k, ax);
+    const float J = box_objective(c, ax.T, ax.gh, ax.gw, lam1, lam2, lam3, s[k]);
+    if (obj) obj[(size_t)b * ax.n + k] = J;
+    if (J == J && (bk < 0 || J < bj)) { bk = k; bj = J; }
+    const float r = (o - s[k]) / den;
+    const int vol = c.L * c.bh * c.bw;
+    if (r >= threshold && (mk < 0 || vol < mv || (vol == mv && r > mr))) { mk = k; mv = vol; mr = r; }
+  }
+  bj_s[tid] = bj; bk_s[tid] = bk; mr_s[tid] = mr; mk_s[tid] = mk; mv_s[tid] = mv;
+  __syncthreads();
+  if (tid != 0) return;
+  for (int t = 1; t < 256; ++t) {
+    const int k2 = bk_s[t];
+    if (k2 >= 0 && (bk < 0 || bj_s[t] < bj || (bj_s[t] == bj && k2 < bk))) { bk = k2; bj = bj_s[t]; }
+    const int m2 = mk_s[t];
+    if (m2 >= 0 && (mk < 0 || mv_s[t] < mv || (mv_s[t] == mv && (mr_s[t] > mr || (mr_s[t] == mr && m2 < mk))))) {
+      mk = m2; mv = mv_s[t]; mr = mr_s[t];
+    }
+  }
+  for (int which = 0; which < 2; ++which) {
+    int* dst = which ? minimal : best;
+    const int k = which ? mk : bk;
+    if (!dst) continue;
+    if (k < 0) {
+      for (int q = 0; q < 6; ++q) dst[b * 6 + q] = -1;
+    } else {
+      const Box c = box_decode(k, ax);
+      dst[b * 6 + 0] = c.a; dst[b * 6 + 1] = c.L; dst[b * 6 + 2] = c.i0;
+      dst[b * 6 + 3] = c.bh; dst[b * 6 + 4] = c.j0; dst[b * 6 + 5] = c.bw;
+    }
+  }
+  if (best_obj) best_obj[b] = bk < 0 ? __builtin_nanf("") : bj;
+}
+
+// Occlusion map from the score grid: drop[b,t,i,j] = mean of (orig_b - s_k) over the candidates whose box covers the
+// cell, in ascending k, NaN scores neither summed nor counted.  One thread per cell; it walks only the covering
+// candidates: per axis the blobs of length l that contain the position start in [max(0, pos-l+1), min(pos, size-l)].
+__device__ __forceinline__ int blob_base(int size, int l) { return (l - 1) * (size + 1) - (l - 1) * l / 2; }
+
+__global__ __launch_bounds__(256) void box_drop_kernel(const float* __restrict__ scores, const float* __restrict__ orig,
+                                                       int B, BoxAxes ax, int max_len, int mh, int mw,
+                                                       float* __restrict__ drop) {
+  const int cells = ax.gh * ax.gw;
+  const size_t e = blockIdx.x * (size_t)256 + threadIdx.x;
+  if (e >= (size_t)B * ax.T * cells) return;
+  const int b = (int)(e / ((size_t)ax.T * cells));
+  const int rem = (int)(e - (size_t)b * ax.T * cells);
+  const int t = rem / cells, cell = rem - t * cells, i = cell / ax.gw, j = cell - i * ax.gw;
+  const float* s = scores + (size_t)b * ax.n;
+  const float o = orig[b];
+  float sum = 0.f;
+  int cnt = 0;
+  for (int lt = 1; lt <= max_len; ++lt)
+    for (int a = max(0, t - lt + 1); a <= min(t, ax.T - lt); ++a) {
+      const int kt = blob_base(ax.T, lt) + a;
+      for (int lh = 1; lh <= mh; ++lh)
+        for (int i0 = max(0, i - lh + 1); i0 <= min(i, ax.gh - lh); ++i0) {
+          const int kh = blob_base(ax.gh, lh) + i0;
+          for (int lw = 1; lw <= mw; ++lw)
+            for (int j0 = max(0, j - lw + 1); j0 <= min(j, ax.gw - lw); ++j0) {
+              const int kw = blob_base(ax.gw, lw) + j0;
+              const float v = s[((size_t)kt * ax.n_h + kh) * ax.n_w + kw];
+              if (v == v) {
+                sum += o - v;
+                ++cnt;
+              }
+            }
+        }
+    }
+  drop[e] = cnt ? sum / (float)cnt : __builtin_nanf("");
+}
+
 static bool st_grid_ok(int gh, int gw) { return gh >= 1 && gh <= ST_MAX_GRID && gw >= 1 && gw <= ST_MAX_GRID; }
+
+// the axes of a checked candidate space (ivf_box_count >= 0)
+static BoxAxes box_axes(int T, int max_len, int gh, int gw, int mh, int mw) {
+  BoxAxes ax;
+  ax.T = T; ax.gh = gh; ax.gw = gw;
+  ax.n_h = ivf_blob_count(gh, mh);
+  ax.n_w = ivf_blob_count(gw, mw);
+  ax.n = ivf_blob_count(T, max_len) * ax.n_h * ax.n_w;
+  return ax;
+}
 
 }  // namespace ivf
 
@@ -594,4 +830,68 @@ extern "C" size_t ivf_stsearch_workspace_bytes(int B, int T, int H, int W, int g
   }
   StScratch sc;
   return sc.carve((size_t)B, (size_t)T, (size_t)H * W, (size_t)gh * gw);
+}
+
+// ---------------------------------------------------------------- one-box search: C-ABI
+extern "C" long long ivf_box_count(int T, int max_len, int gh, int gw, int mh, int mw) {
+  if (T < 1 || T > ST_MAX_T || max_len < 1 || max_len > T || !st_grid_ok(gh, gw) || mh < 1 || mh > gh || mw < 1 ||
+      mw > gw) {
+    set_error("box_count: need 1 <= max_len (%d) <= T (%d) <= %d, 1 <= mh (%d) <= gh (%d) <= %d, 1 <= mw (%d) <= gw (%d) <= %d",
+              max_len, T, ST_MAX_T, mh, gh, ST_MAX_GRID, mw, gw, ST_MAX_GRID);
+    return -1;
+  }
+  return (long long)ivf_blob_count(T, max_len) * ivf_blob_count(gh, mh) * ivf_blob_count(gw, mw);   // < 2^31 at the limits
+}
+
+extern "C" int ivf_box_stage(const float* x, int b, int C, int T, int H, int W, const float* A_H, const float* A_W, int gh,
+                             int gw, int max_len, int mh, int mw, long long first, int count, float* p, int out_cpad,
+                             ivf_stream_t stream) {
+  IVF_CHECK_ARG(x && A_H && A_W && p, "box_stage: null pointer");
+  IVF_CHECK_ARG(b > 0 && C > 0 && H > 0 && W > 0 && (long long)H * W <= 0x7fffffffLL, "box_stage: bad dims");
+  const long long n = ivf_box_count(T, max_len, gh, gw, mh, mw);
+  if (n < 0) return IVF_ERR_BAD_ARG;
+  IVF_CHECK_ARG(first >= 0 && count > 0 && count <= 65535 && first + count <= (long long)b * n,
+                "box_stage: rows [%lld, %lld) outside the %lld candidates of %d clips (at most 65535 rows a call)", first,
+                first + count, (long long)b * n, b);
+  IVF_CHECK_ARG(out_cpad == 0 || (out_cpad == 4 && C <= 4),
+                "box_stage: out_cpad must be 0 (NCTHW) or 4 (16-byte channels-last, C <= 4)");
+  const BoxAxes ax = box_axes(T, max_len, gh, gw, mh, mw);
+  const int HW = H * W;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(cdiv(HW, 256), count), block(256);
+  if (out_cpad == 0)
+    hipLaunchKernelGGL(box_stage_ncthw_kernel, grid, block, 0, s, x, A_H, A_W, p, C, W, HW, ax, first);
+  else if (T == 16)
+    hipLaunchKernelGGL(box_stage_cl4_kernel<16>, grid, block, 0, s, x, A_H, A_W, p, C, W, HW, ax, first);
+  else if (T == 32)
+    hipLaunchKernelGGL(box_stage_cl4_kernel<32>, grid, block, 0, s, x, A_H, A_W, p, C, W, HW, ax, first);
+  else
+    hipLaunchKernelGGL(box_stage_cl4_kernel<0>, grid, block, 0, s, x, A_H, A_W, p, C, W, HW, ax, first);
+  IVF_CHECK_LAUNCH();
+  return IVF_OK;
+}
+
+extern "C" int ivf_box_select(const float* scores, const float* orig, const float* full, int b, int T, int gh, int gw,
+                              int max_len, int mh, int mw, float lam1, float lam2, float lam3, float threshold, int* best,
+                              float* best_obj, float* obj, int* minimal, ivf_stream_t stream) {
+  IVF_CHECK_ARG(scores && orig && full && best, "box_select: null pointer");
+  IVF_CHECK_ARG(b > 0, "box_select: bad batch %d", b);
+  if (ivf_box_count(T, max_len, gh, gw, mh, mw) < 0) return IVF_ERR_BAD_ARG;
+  hipLaunchKernelGGL(box_select_kernel, dim3(b), dim3(256), 0, (hipStream_t)stream, scores, orig, full,
+                     box_axes(T, max_len, gh, gw, mh, mw), lam1, lam2, lam3, threshold, best, best_obj, obj, minimal);
+  IVF_CHECK_LAUNCH();
+  return IVF_OK;
+}
+
+extern "C" int ivf_box_drop(const float* scores, const float* orig, int b, int T, int gh, int gw, int max_len, int mh,
+                            int mw, float* drop, ivf_stream_t stream) {
+  IVF_CHECK_ARG(scores && orig && drop, "box_drop: null pointer");
+  IVF_CHECK_ARG(b > 0, "box_drop: bad batch %d", b);
+  if (ivf_box_count(T, max_len, gh, gw, mh, mw) < 0) return IVF_ERR_BAD_ARG;
+  const long long cells = (long long)b * T * gh * gw;
+  IVF_CHECK_ARG(cdiv(cells, 256) <= 0x7fffffffLL, "box_drop: too many cells");
+  hipLaunchKernelGGL(box_drop_kernel, dim3(cdiv(cells, 256)), dim3(256), 0, (hipStream_t)stream, scores, orig, b,
+                     box_axes(T, max_len, gh, gw, mh, mw), max_len, mh, mw, drop);
+  IVF_CHECK_LAUNCH();
+  return IVF_OK;
 }

@@ -271,6 +271,26 @@ class _Engine:
             L.check(self._fn("stperturbed_forward")(self._h, L.ptr(x), b, L.ptr(M), L.ptr(probs), L.stream()))
         return probs
 
+    def box_scores(self, x, target, grid, sigma=None, max_len=None, max_box=None):
+        """Exhaustive one-box search grid (maskType 'stcombi', ivf_*_box_scores): scores [b, n] of target[clip] with the
+        clip frozen per pixel by every one-box binary mask on `grid` (expanded as st_expand expands it), in the order of
+        ivf_search.box_candidates(T, grid, max_len, max_box).  max_len defaults to T, max_box to the whole grid; b may
+        exceed max_batch (chunks of the plan's max_batch rows)."""
+        gh, gw, _, AH, AW = self._st_axes(grid, sigma)
+        x = self._clip(x, any_batch=True)
+        b, T = x.shape[0], self.clip_shape[1]
+        ml = T if max_len is None else int(max_len)
+        mh, mw = (gh, gw) if max_box is None else (int(v) for v in max_box)
+        n = L.lib().ivf_box_count(T, ml, gh, gw, mh, mw)
+        if n < 0:
+            raise L.IvfError(L.lib().ivf_last_error().decode())
+        tgt = self._targets(target, b)
+        scores = torch.empty(b, n, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(self._fn("box_scores")(self._h, L.ptr(x), b, L.ptr(tgt), L.ptr(AH), L.ptr(AW), gh, gw, ml, mh, mw,
+                                           L.ptr(scores), L.stream()))
+        return scores
+
     def argmax(self, probs):
         b = probs.shape[0]
         t = torch.empty(b, dtype=torch.int32, device=self.device)

@@ -46,8 +46,14 @@ def _unwrap(model):
 def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMaskType="freeze", classOI=None,
                     verbose=True, doGradCam=False, runTempMask=True, flavour="smth", sub_dir="run0",
                     results_path="results/", gradcam_size=None, write_files=True, device=None, visualise=True,
-                    mask_mode="central", max_mask_length=None, blob_batch=32, mask_grid=None, mask_sigma=None, lam3=None):
-    """mask_mode 'spacetime' (the drivers' maskType='spacetime', an extension: DESIGN 11) searches a mask per frame
+                    mask_mode="central", max_mask_length=None, blob_batch=32, mask_grid=None, mask_sigma=None, lam3=None,
+                    max_box=None):
+    """mask_mode 'stcombi' (the drivers' maskType='stcombi', an extension: DESIGN 12) scores every one-box space-time
+    mask (one temporal blob of length <= max_mask_length times one rectangle of at most max_box grid cells) and keeps the
+    minimiser of the spacetime loss; its plan holds at least blob_batch clips, its records also carry st_mask (binary),
+    box_start, box_length, box_rows (i0, bh), box_cols (j0, bw) and box_drop [T,gh,gw], and the strips and PNGs are
+    made from the expanded box as for 'spacetime'.
+    mask_mode 'spacetime' (the drivers' maskType='spacetime', an extension: DESIGN 11) searches a mask per frame
     and grid cell (mask_grid, mask_sigma, lam3: see ivf_search.MaskSearch); its records also carry st_mask
     [T,gh,gw], the heat-map strips blend the expanded mask where they blend the Grad-CAM map otherwise, and the KTH
     flavour's perturbed-frame PNGs show the per-pixel freeze that was searched (the mark in their corner is time_mask).
@@ -75,16 +81,16 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
         if not keep:
             continue
         xs = x[keep].contiguous()
-        eng = net._engine_for(xs, min_batch=blob_batch) if mask_mode == "combi" else net._engine_for(xs)
+        eng = net._engine_for(xs, min_batch=blob_batch) if mask_mode in ("combi", "stcombi") else net._engine_for(xs)
         search = ivf_search.MaskSearch(eng, lam1, lam2, N, temporalMaskType, threshold=0.9, lr=0.2,
                                        grad_cam_type=hyper_params.get("gradCamType", "guessed"),
                                        do_gradcam=doGradCam, run_temp_mask=runTempMask,
                                        normalize_per_frame=True, gradcam_size=gradcam_size, mask_mode=mask_mode,
                                        max_mask_length=max_mask_length, mask_grid=mask_grid, mask_sigma=mask_sigma,
-                                       lam3=lam3)
+                                       lam3=lam3, max_box=max_box)
         res = search.run(xs, labels[keep])
-        host = {k: v.detach().cpu() for k, v in res.items() if k != "gradcam"}
-        spacetime = runTempMask and mask_mode == "spacetime"
+        host = {k: v.detach().cpu() for k, v in res.items() if k not in ("gradcam", "box_scores")}
+        spacetime = runTempMask and mask_mode in ("spacetime", "stcombi")
         st_maps = eng.st_expand(res["st_mask"], search.st_grid(xs), mask_sigma) if spacetime and write_files and visualise \
             else None
         st_pert = eng.st_freeze(xs, st_maps) if st_maps is not None and flavour != "smth" else None   # what was searched
@@ -117,6 +123,10 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                             blob_scores=host["blob_scores"][j].numpy())
                 if spacetime:
                     time_results[-1].update(st_mask=host["st_mask"][j].numpy())
+                if runTempMask and mask_mode == "stcombi":
+                    bx = [int(v) for v in host["box"][j]]
+                    time_results[-1].update(box_start=bx[0], box_length=bx[1], box_rows=(bx[2], bx[3]),
+                                            box_cols=(bx[4], bx[5]), box_drop=host["box_drop"][j].numpy())
                 tmask = res["time_mask"][j].clone()     # the clip's own [T] tensor, as the reference's time_mask
                 if verbose:
                     print("resulting mask is: ", tmask)

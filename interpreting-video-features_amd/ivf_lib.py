@@ -94,6 +94,11 @@ _SIGS = {
     "ivf_stmask_reg": (c_int, [_P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P]),
     "ivf_stmask_step": (c_int, [_P] * 9 + [_I] * 5 + [_F] * 4 + [_P]),
     "ivf_stsearch_workspace_bytes": (c_size_t, [_I] * 6),
+    # one-box search (maskType 'stcombi', documented extension)
+    "ivf_box_count": (ctypes.c_longlong, [_I] * 6),
+    "ivf_box_stage": (c_int, [_P] + [_I] * 5 + [_P, _P] + [_I] * 5 + [ctypes.c_longlong, _I, _P, _I, _P]),
+    "ivf_box_select": (c_int, [_P, _P, _P] + [_I] * 7 + [_F] * 4 + [_P] * 5),
+    "ivf_box_drop": (c_int, [_P, _P] + [_I] * 7 + [_P, _P]),
     "ivf_clip_ingest_u8": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ivf_conv3d": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
     "ivf_bn_fold": (c_int, [_P, _P, _P, _P, _F, _P, _P, _I, _P]),
@@ -135,6 +140,7 @@ _SIGS = {
     "ivf_i3d_stsearch": (c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I] + [_F] * 7 + [_I, _I, _P, _P, _P]),
     "ivf_i3d_stperturbed_forward": (c_int, [_P, _P, _I, _P, _P, _P]),
     "ivf_i3d_blob_scores": (c_int, [_P, _P, _I, _P, _I, _I, _P, _P]),
+    "ivf_i3d_box_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 5 + [_P, _P]),
     "ivf_i3d_gradcam": (c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "ivf_i3d_gradcam_layer": (c_int, [_P, _P, _I, _P, c_char_p, _I, _I, _I, _P, _P, _P]),
     "ivf_i3d_conv_flops_per_clip": (ctypes.c_double, [_P]),
@@ -170,6 +176,7 @@ _SIGS = {
     "ivf_clstm_stsearch": (c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I] + [_F] * 7 + [_I, _I, _P, _P, _P]),
     "ivf_clstm_stperturbed_forward": (c_int, [_P, _P, _I, _P, _P, _P]),
     "ivf_clstm_blob_scores": (c_int, [_P, _P, _I, _P, _I, _I, _P, _P]),
+    "ivf_clstm_box_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 5 + [_P, _P]),
     "ivf_clstm_gradcam_reduce": (c_int, [_P, _P, POINTER(c_int), _I, _P, _P, _I, _I, _I, _I, _P]),
     "ivf_clstm_set_cam_steps": (c_int, [_P, POINTER(c_int), _I]),
     "ivf_clstm_gradcam": (c_int, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),

@@ -130,22 +130,104 @@ def blob_masks(best, T):
     return ((u >= a) & (u < a + ln)).float()
 
 
+def _box_limits(T, grid, max_len, max_box):
+    gh, gw = (int(v) for v in grid)
+    ml = int(T) if max_len is None else int(max_len)
+    mh, mw = (gh, gw) if max_box is None else (int(v) for v in max_box)
+    n = L.lib().ivf_box_count(int(T), ml, gh, gw, mh, mw)
+    if n < 0:
+        raise L.IvfError(L.lib().ivf_last_error().decode())
+    return gh, gw, ml, mh, mw, n
+
+
+def box_candidates(T, grid, max_len=None, max_box=None):
+    """The one-box candidates of maskType 'stcombi' as a host int64 table [n, 6] of (a, L, i0, bh, j0, bw): frames
+    [a, a+L), grid rows [i0, i0+bh), grid columns [j0, j0+bw), L <= max_len (default T), (bh, bw) <= max_box (default
+    the grid).  Row k = (kt * n_h + kh) * n_w + kw, each axis in the order of blob_candidates."""
+    gh, gw, ml, mh, mw, n = _box_limits(T, grid, max_len, max_box)
+    t, h, w = blob_candidates(T, ml), blob_candidates(gh, mh), blob_candidates(gw, mw)
+    nt, nh, nw = t.shape[0], h.shape[0], w.shape[0]
+    out = torch.cat([t[:, None, None, :].expand(nt, nh, nw, 2), h[None, :, None, :].expand(nt, nh, nw, 2),
+                     w[None, None, :, :].expand(nt, nh, nw, 2)], dim=3)
+    return out.reshape(n, 6).contiguous()
+
+
+def box_select(scores, orig, full, T, grid, max_len=None, max_box=None, lam1=0.01, lam2=0.02, lam3=None, threshold=0.9,
+               want_obj=False):
+    """ivf_box_select on a score grid [b, n]: dict of device tensors best [b,6] (a, L, i0, bh, j0, bw of argmin J),
+    objective [b] (its J), minimal [b,6] (smallest sufficient box, all -1 if none), index [b] (k of best, -1 if none)
+    and, with want_obj, obj [b,n].  lam3 defaults to lam2."""
+    gh, gw, ml, mh, mw, n = _box_limits(T, grid, max_len, max_box)
+    s = L.f32c(scores)
+    L.require_gpu(s)
+    b = s.shape[0]
+    if tuple(s.shape) != (b, n):
+        raise L.IvfError(f"scores must be [b,{n}], got {tuple(s.shape)}")
+    orig, full = L.f32c(orig.reshape(b)), L.f32c(full.reshape(b))
+    best = torch.empty(b, 6, dtype=torch.int32, device=s.device)
+    minimal = torch.empty(b, 6, dtype=torch.int32, device=s.device)
+    bobj = torch.empty(b, device=s.device)
+    obj = torch.empty_like(s) if want_obj else None
+    with torch.cuda.device(s.device):
+        L.check(L.lib().ivf_box_select(L.ptr(s), L.ptr(orig), L.ptr(full), b, int(T), gh, gw, ml, mh, mw, float(lam1),
+                                       float(lam2), float(lam2 if lam3 is None else lam3), float(threshold), L.ptr(best),
+                                       L.ptr(bobj), L.ptr(obj), L.ptr(minimal), L.stream()))
+    best = best.long()
+    nh, nw = L.lib().ivf_blob_count(gh, mh), L.lib().ivf_blob_count(gw, mw)
+    k = (blob_index(best[:, 0:2], int(T)) * nh + blob_index(best[:, 2:4], gh)) * nw + blob_index(best[:, 4:6], gw)
+    out = dict(best=best, objective=bobj, minimal=minimal.long(), index=torch.where(best[:, 1] >= 1, k, torch.full_like(k, -1)))
+    if want_obj:
+        out["obj"] = obj
+    return out
+
+
+def box_drop(scores, orig, T, grid, max_len=None, max_box=None):
+    """ivf_box_drop: the occlusion map [b,T,gh,gw] of a score grid [b,n] -- per cell the mean of orig - score over the
+    candidates whose box covers it."""
+    gh, gw, ml, mh, mw, n = _box_limits(T, grid, max_len, max_box)
+    s = L.f32c(scores)
+    L.require_gpu(s)
+    b = s.shape[0]
+    if tuple(s.shape) != (b, n):
+        raise L.IvfError(f"scores must be [b,{n}], got {tuple(s.shape)}")
+    orig = L.f32c(orig.reshape(b))
+    drop = torch.empty(b, int(T), gh, gw, device=s.device)
+    with torch.cuda.device(s.device):
+        L.check(L.lib().ivf_box_drop(L.ptr(s), L.ptr(orig), b, int(T), gh, gw, ml, mh, mw, L.ptr(drop), L.stream()))
+    return drop
+
+
+def box_masks(best, T, grid):
+    """Binary float S [b,T,gh,gw] of (a, L, i0, bh, j0, bw) rows [b,6] (all zero for L < 1)."""
+    gh, gw = (int(v) for v in grid)
+    dev = best.device
+
+    def axis(n, lo, ln):
+        u = torch.arange(n, device=dev)[None]
+        return ((u >= lo[:, None]) & (u < (lo + ln)[:, None])).float()
+    t, h, w = axis(int(T), best[:, 0], best[:, 1]), axis(gh, best[:, 2], best[:, 3]), axis(gw, best[:, 4], best[:, 5])
+    return (t[:, :, None, None] * h[:, None, :, None] * w[:, None, None, :]).contiguous()
+
+
 class MaskSearch:
     def __init__(self, engine, lam1=0.01, lam2=0.02, n_iter=300, mask_type="freeze", threshold=0.9,
                  lr=0.2, grad_cam_type="guessed", do_gradcam=True, run_temp_mask=True,
                  normalize_per_frame=True, gradcam_size=None, mask_mode="central", max_mask_length=None,
-                 mask_grid=None, mask_sigma=None, lam3=None):
+                 mask_grid=None, mask_sigma=None, lam3=None, max_box=None):
         """mask_mode 'central': init_mask('central') + n_iter Adam steps (smth:188-214); 'combi': the exhaustive
         one-blob search (smth:137-141) over masks of length <= max_mask_length (default T), no gradient descent;
         'spacetime' (an extension without a counterpart in the reference): the gradient search on a mask per
         frame and grid cell -- mask_grid (gh, gw) (default one cell per 32 input pixels: 7x7 at 224^2, 4x5 at
         120x160), mask_sigma the blur in input pixels (default 0.5 H / gh), lam3 the spatial TV weight (default lam2);
-        the perturbation is the per-pixel freeze."""
-        if mask_mode not in ("central", "combi", "spacetime"):
-            raise L.IvfError(f"mask_mode must be 'central', 'combi' or 'spacetime', got {mask_mode!r}")
-        if mask_mode == "spacetime" and mask_type != "freeze":
-            raise L.IvfError("mask_mode 'spacetime' perturbs by freezing only")
-        self.mask_mode, self.max_mask_length = mask_mode, max_mask_length
+        the perturbation is the per-pixel freeze.  'stcombi'  is to 'spacetime' what 'combi' is to 'central':
+        every box of one temporal blob (length <= max_mask_length) times one rectangle of grid cells (at most max_box =
+        (mh, mw), default the whole grid) is scored by a forward pass and the minimiser of the spacetime loss picked on
+        the device; mask_grid, mask_sigma and lam3 as for 'spacetime', n_iter unused."""
+        if mask_mode not in ("central", "combi", "spacetime", "stcombi"):
+            raise L.IvfError(f"mask_mode must be 'central', 'combi', 'spacetime' or 'stcombi', got {mask_mode!r}")
+        if mask_mode in ("spacetime", "stcombi") and mask_type != "freeze":
+            raise L.IvfError(f"mask_mode {mask_mode!r} perturbs by freezing only")
+        self.mask_mode, self.max_mask_length, self.max_box = mask_mode, max_mask_length, max_box
         self.mask_grid, self.mask_sigma, self.lam3 = mask_grid, mask_sigma, lam3
         self.engine = engine
         self.lam1, self.lam2, self.n_iter = float(lam1), float(lam2), int(n_iter)
@@ -175,6 +257,8 @@ class MaskSearch:
             self._run_combi(x, target, probs, out)
         elif self.run_temp_mask and self.mask_mode == "spacetime":
             self._run_spacetime(x, target, probs, out, want_traj)
+        elif self.run_temp_mask and self.mask_mode == "stcombi":
+            self._run_stcombi(x, target, probs, out)
         elif self.run_temp_mask:
             raw, info = init_masks_central(eng, x, target, probs[idx, target.long()], self.threshold,
                                            self.mask_type)                   # smth:188-190
@@ -259,6 +343,39 @@ class MaskSearch:
         out["snapped"] = mean > 0.5
         if want_traj:
             out["traj"] = traj
+
+    def _run_stcombi(self, x, target, probs, out):
+        """maskType 'stcombi': score every one-box mask, pick the argmin of the spacetime loss on the device; st_mask is
+        the binary S of the best box, time_mask its spatial mean per frame (the call of _run_spacetime), and from
+        time_mask the reverse score, ranking and snapped mask with the code of the temporal search."""
+        eng = self.engine
+        b, T = x.shape[0], x.shape[2]
+        dev = x.device
+        idx = torch.arange(b, device=dev)
+        tl = target.long()
+        grid = gh, gw = self.st_grid(x)
+        orig = probs[idx, tl]
+        full = eng.perturbed_forward(x, torch.ones(b, T, device=dev), "freeze")[idx, tl]     # mask.py:123-128
+        scores = eng.box_scores(x, target, grid, self.mask_sigma, self.max_mask_length, self.max_box)
+        sel = box_select(scores, orig, full, T, grid, self.max_mask_length, self.max_box, self.lam1, self.lam2, self.lam3,
+                         self.threshold)
+        S = box_masks(sel["best"], T, grid)
+        mean = torch.empty(b, T, device=dev)
+        ah, aw = torch.full((1, gh), 1.0 / gh, device=dev), torch.full((1, gw), 1.0 / gw, device=dev)
+        with torch.cuda.device(dev):
+            L.check(L.lib().ivf_stmask_expand_fwd(L.ptr(S), L.ptr(ah), L.ptr(aw), L.ptr(mean), b, T, gh, gw, 1, 1, L.stream()))
+        k = sel["index"]
+        out["st_mask"] = S
+        out["time_mask"] = mean
+        out["freeze_score"] = torch.where(k >= 0, scores[idx, k.clamp(min=0)], torch.full((b,), float("nan"), device=dev))
+        out["reverse_score"] = eng.perturbed_forward(x, mean, "reverse")[idx, tl]
+        out["ranking"] = frame_ranking(mean)
+        out["snapped"] = mean > 0.5
+        out["box"] = sel["best"]
+        out["box_objective"] = sel["objective"]
+        out["box_minimal"] = sel["minimal"]
+        out["box_scores"] = scores
+        out["box_drop"] = box_drop(scores, orig, T, grid, self.max_mask_length, self.max_box)
 
 
 RECORD_INT_FIELDS = ("clip_id", "pred_class", "target")
