@@ -693,6 +693,10 @@ int ivf_tfclstm_bind(ivf_tfclstm_t* net, void* weights_arena, void* workspace);
 /* conv output (Ho, Wo), pooled (Hp, Wp) and filters of a block; inputs of the dense head */
 int ivf_tfclstm_layer_dims(const ivf_tfclstm_t* net, int layer, int* Ho, int* Wo, int* Hp, int* Wp, int* units);
 int ivf_tfclstm_fc_inputs(const ivf_tfclstm_t* net);
+/* Workspace views of one block after a forward / backward (test support): its output sequence H [b,T,F,Ho,Wo], its
+ * pooled output X [b,T,F,Hp,Wp] and the gradient dX that arrives at X (same shape); every output optional,
+ * dimensions from ivf_tfclstm_layer_dims. */
+int ivf_tfclstm_layer_buffers(ivf_tfclstm_t* net, int layer, const float** H, const float** X, const float** dX);
 int ivf_tfclstm_load_layer(ivf_tfclstm_t* net, int layer, const float* kernel, const float* recurrent_kernel,
                            const float* bias, ivf_stream_t stream);
 int ivf_tfclstm_load_head(ivf_tfclstm_t* net, const float* dense_kernel, const float* dense_bias, ivf_stream_t stream);

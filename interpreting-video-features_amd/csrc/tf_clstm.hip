@@ -495,6 +495,16 @@ extern "C" int ivf_tfclstm_layer_dims(const ivf_tfclstm_t* n, int layer, int* Ho
   return IVF_OK;
 }
 
+extern "C" int ivf_tfclstm_layer_buffers(ivf_tfclstm_t* n, int layer, const float** H, const float** X, const float** dX) {
+  IVF_CHECK_ARG(n && n->ws, "tfclstm_layer_buffers: not bound");
+  IVF_CHECK_ARG(layer >= 0 && layer < (int)n->L.size(), "tfclstm_layer_buffers: bad layer");
+  const TfLayerPlan& p = n->L[layer];
+  if (H) *H = n->wsf(p.H_off);
+  if (X) *X = n->wsf(p.X_off);
+  if (dX) *dX = n->wsf(p.dX_off);
+  return IVF_OK;
+}
+
 extern "C" int ivf_tfclstm_load_layer(ivf_tfclstm_t* n, int layer, const float* kernel, const float* recurrent_kernel,
                                       const float* bias, ivf_stream_t stream) {
   IVF_CHECK_ARG(n && n->wa, "tfclstm_load_layer: bind first");

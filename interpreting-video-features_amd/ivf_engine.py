@@ -589,6 +589,20 @@ class TFCLSTMEngine(_Engine):
         L.check(L.lib().ivf_tfclstm_layer_dims(self._h, i, *[byref(a) for a in v]))
         return tuple(a.value for a in v)
 
+    def layer_state(self, layer, b):
+        """Copies of what the last forward / backward left for a block (test support): its output sequence H
+        [b,T,F,Ho,Wo], its pooled output X and the gradient dX that arrived at X, both [b,T,F,Hp,Wp]."""
+        H, X, dX = c_void_p(), c_void_p(), c_void_p()
+        L.check(L.lib().ivf_tfclstm_layer_buffers(self._h, int(layer), byref(H), byref(X), byref(dX)))
+        Ho, Wo, Hp, Wp, Fu = self.layer_dims(layer)
+        T = self.clip_shape[1]
+        out = []
+        for p, (h, w) in ((H, (Ho, Wo)), (X, (Hp, Wp)), (dX, (Hp, Wp))):
+            off = p.value - self._ws.data_ptr()
+            n = b * T * Fu * h * w
+            out.append(self._ws[off:off + 4 * n].view(torch.float32).view(b, T, Fu, h, w).clone())
+        return tuple(out)
+
     def load_weights(self, layers, dense_w, dense_b):
         """layers: [(kernel [kh,kw,Cin,4F], recurrent_kernel [kh,kw,F,4F], bias [4F])] in Keras layouts;
         dense_w [inputs, classes], dense_b [classes]."""

@@ -190,6 +190,7 @@ _SIGS = {
     "ivf_tfclstm_bind": (c_int, [_P, _P, _P]),
     "ivf_tfclstm_layer_dims": (c_int, [_P, _I] + [POINTER(c_int)] * 5),
     "ivf_tfclstm_fc_inputs": (c_int, [_P]),
+    "ivf_tfclstm_layer_buffers": (c_int, [_P, _I] + [POINTER(c_void_p)] * 3),
     "ivf_tfclstm_load_layer": (c_int, [_P, _I, _P, _P, _P, _P]),
     "ivf_tfclstm_load_head": (c_int, [_P, _P, _P, _P]),
     "ivf_tfclstm_forward": (c_int, [_P, _P, _I, _P, _P, _P]),

@@ -257,3 +257,14 @@ def test_clstm_persistent_recurrence_matches_stepwise_and_reference(C, golden):
     assert rel_err(dxn.ravel()[g[f'c{C}_dx_idx']], g[f'c{C}_dx_val']) < 2e-3
     note(f"clstm persistent vs stepwise (C={C}): logits {rel_err(lb[:2].cpu().numpy(), ls.cpu().numpy()):.2e}, "
          f"dx {rel_err(dxb[:2].cpu().numpy(), dxs.cpu().numpy()):.2e}")
+
+
+def test_clstm_resumed_search_continues_bit_for_bit():
+    """4 iterations in one call == 2 + 2 through the returned state (first_step = steps done + 1): raw mask, Adam
+    moments and trajectory rows bit for bit."""
+    import ivf_recipe as R
+    from search_resume import check_resumed_search
+    eng = _engine(1, B=1)
+    x = torch.from_numpy(R.clip(3, 1, 32, 120, 160) / 255.0).float()[None].cuda()
+    raw0 = torch.linspace(-2.0, 2.0, 32)[None].cuda().contiguous()
+    check_resumed_search(lambda raw, n, state: eng.search(x, [2], raw, 0.02, 0.04, n, state=state), raw0, 4, 2)

@@ -663,3 +663,14 @@ def test_gradcam_other_target_layers(s16, layer, golden):
     # the ordinary passes are untouched by the ungated Grad-CAM pass before them
     p2 = s16.forward(x)
     assert torch.equal(p2, probs)
+
+
+def test_resumed_search_continues_bit_for_bit(s16):
+    """4 iterations in one call == 2 + 2 through the returned state (first_step = steps done + 1): raw mask, Adam
+    moments and trajectory rows bit for bit, in every arithmetic mode."""
+    import ivf_recipe as R
+    from search_resume import check_resumed_search
+    x = torch.from_numpy(R.clip(21))[None].cuda()
+    target = s16.argmax(s16.forward(x)).tolist()
+    raw0 = torch.linspace(-2.0, 2.0, 16)[None].cuda().contiguous()
+    check_resumed_search(lambda raw, n, state: s16.search(x, target, raw, 0.01, 0.02, n, state=state), raw0, 4, 2)

@@ -311,6 +311,18 @@ def test_clstm_1x1_grid_reduces_to_the_temporal_search(chain):
     assert float((torch.sigmoid(rb.view(b, T)) - torch.sigmoid(ra)).abs().max()) < 1e-2
 
 
+def test_resumed_st_search_continues_bit_for_bit(chain):
+    """4 iterations of the spacetime loop in one call == 2 + 2 through the returned state (first_step = steps done +
+    1): raw, Adam moments and trajectory rows bit for bit"""
+    from search_resume import check_resumed_search
+    eng, c = chain
+    x = c['x'].cuda()
+
+    def search(raw, n, state):
+        return eng.st_search(x, c['targets'], raw, 0.01, 0.02, n, R.CHAIN_GRID, R.CHAIN_SIGMA, lam3=0.03, state=state)
+    check_resumed_search(search, c['raw'].cuda().contiguous(), 4, 2)
+
+
 # ---------------------------------------------------------------------------------------------------- I3D
 @pytest.fixture(scope="module", params=["fp32", "bf16x3", "bf16x6"])
 def s16(request):

@@ -97,3 +97,14 @@ def test_tfclstm_search_and_gradcam():
     note(f"tf-style clstm search: 6-iteration trajectory and final mask vs the torch restatement within 1e-3 (unpinned vs TF)")
     with pytest.raises(Exception):
         eng.gradcam(xg[:1], [0], normalization_mode="clip")
+
+
+def test_tfclstm_resumed_search_continues_bit_for_bit():
+    """5 iterations in one call == 2 + 3 through the returned state: raw mask, Adam moments and trajectory rows bit
+    for bit.  first_step also forms eps_hat(step) = eps / sqrt(1 - beta2^step) of tf.train.Adam's update here, so a
+    resumed call that counted from 1 again would move the mask."""
+    from search_resume import check_resumed_search
+    eng, w, x, kw = _setup()
+    xg = x.cuda()
+    raw0 = (torch.rand(2, 8, generator=torch.Generator().manual_seed(5)) * 4 - 2).cuda().contiguous()
+    check_resumed_search(lambda raw, n, state: eng.search(xg, [1, 3], raw, 0.01, 0.02, n, state=state), raw0, 5, 2)

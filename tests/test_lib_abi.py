@@ -63,6 +63,29 @@ def test_plan_is_host_only_and_sized():
     lib.ivf_i3d_destroy(h)
 
 
+def test_tfclstm_plan_is_sized_as_before_the_layer_view():
+    """ivf_tfclstm_layer_buffers only looks into the plan: workspace and weights arena of two configurations keep the
+    sizes they had before the accessor existed (carve order unchanged), and an unbound plan has no views."""
+    import ivf_lib as L
+    lib = L.lib()
+    for geom, units, kernel, stride, padding, only_last, want in (
+            ((2, 1, 8, 30, 40), (4, 6), (3, 5), 2, 0, 1, (1431040, 20480)),
+            ((4, 2, 4, 9, 11), (3,), (3, 3), 1, 1, 0, (401920, 7936))):
+        cfg = L.TFCLSTMConfig()
+        cfg.B, cfg.C, cfg.T, cfg.H, cfg.W = geom
+        cfg.layers = len(units)
+        for i, u in enumerate(units):
+            cfg.units[i] = u
+        cfg.kh, cfg.kw = kernel
+        cfg.stride, cfg.padding, cfg.recurrent_hard_sigmoid, cfg.only_last, cfg.num_classes = stride, padding, 1, only_last, 5
+        h = ctypes.c_void_p()
+        L.check(lib.ivf_tfclstm_create(ctypes.byref(cfg), ctypes.byref(h)))
+        assert (lib.ivf_tfclstm_workspace_bytes(h), lib.ivf_tfclstm_weights_bytes(h)) == want
+        p = ctypes.c_void_p()
+        assert lib.ivf_tfclstm_layer_buffers(h, 0, ctypes.byref(p), None, None) == -1 and not p.value
+        lib.ivf_tfclstm_destroy(h)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU refusal")
 def test_no_cpu_fallback():
     import ivf_lib as L
