@@ -184,6 +184,33 @@ int ivf_stmask_step(float* raw, const float* sig, const float* dscore_dsig, cons
  * 0 with the message set for a shape the loop refuses. */
 size_t ivf_stsearch_workspace_bytes(int B, int T, int H, int W, int gh, int gw);
 
+/* ------------------------------------------------------------------ Integrated Gradients for video (csrc/ig_ops.hip)
+ * An EXTENSION with no counterpart in the reference.  Path x(alpha) = x0 + alpha (x - x0) from a baseline
+ * clip x0 to the clip x [b,C,T,HW]; nodes alpha [K] and weights w [K] are device arrays (any quadrature rule).
+ * base_kind: 0 'frozen' (x0 = frame 0 of the row's own clip at every frame, mask.py:123-128), 1 'constant' (base_value
+ * everywhere), 2 'clip' (base [b,C,T,HW]); base is read for kind 2 only.  The (clip, node) rows are numbered
+ * g = clip * K + k.  No float atomics; every sum has a fixed order, so a clip's results depend neither on the batch it
+ * ran in nor on how the rows were cut into windows.
+ *
+ * ivf_ig_stage: rows [first, first+count) into out; row j is clip (first+j)/K at node (first+j)%K, each element
+ * fmaf(alpha, x - x0, x0): exact where x == x0 and at alpha == 0.  layout as the mask kernels name it: 0 NCTHW
+ * [count,C,T,HW], 4 16-byte channels-last pixels [count,T,HW,4] (C <= 4, pad lanes written +0.0). */
+int ivf_ig_stage(const float* x, int base_kind, const float* base, float base_value, const float* alpha, int b, int C,
+                 int T, int HW, int K, long long first, int count, float* out, int layout, ivf_stream_t stream);
+/* Gsum [b,C,T,HW] (NCTHW, zeroed by the caller once per call) += the window's rows of din (layout as above, row j the
+ * gradient of row first+j): per element acc = fmaf(w[k], g, acc) over the window's rows of its clip, k ascending.  Pad
+ * lanes of din are never read into a result. */
+int ivf_ig_accumulate(const float* din, int layout, const float* w, int K, long long first, int count, float* Gsum, int b,
+                      int C, int T, int HW, ivf_stream_t stream);
+/* A = (x - x0) Gsum; ig_map [b,T,HW] = sum_c A (c ascending); frames [b,T] = sum_px ig_map and abs_frames [b,T] =
+ * sum_px sum_c |A| (thread-order partial sums, a wave64 shuffle tree, then the waves in order); total [b] = sum_t
+ * frames (t ascending). */
+int ivf_ig_finish(const float* x, int base_kind, const float* base, float base_value, const float* Gsum, int b, int C,
+                  int T, int HW, float* ig_map, float* frames, float* abs_frames, float* total, ivf_stream_t stream);
+/* Bytes of caller-owned scratch of ivf_{i3d,clstm}_ig for b clips and K nodes (Gsum, the per-row targets, the row
+ * scores); 0 with the message set for bad dims. */
+size_t ivf_ig_workspace_bytes(int b, int C, int T, int HW, int K);
+
 /* ------------------------------------------------------------------ exhaustive one-box search (maskType 'stcombi')
  * The gradient-free counterpart of 'spacetime', as 'combi' is of the temporal gradient search; an extension as well.
  * A candidate (a, L, i0, bh, j0, bw) is the binary S that is 1 on frames [a, a+L), grid rows [i0, i0+bh) and grid
@@ -512,6 +539,19 @@ int ivf_i3d_blob_scores(ivf_i3d_t* net, const float* x, int b, const int* target
 int ivf_i3d_box_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W, int gh,
                       int gw, int max_len, int mh, int mw, float* scores, ivf_stream_t stream);
 
+/* Integrated Gradients of b clips through this plan (extension, see ivf_ig_*): the b*K path points run in chunks of the
+ * plan's B rows across clip boundaries (ivf_ig_stage -> forward -> backward -> ivf_ig_accumulate), then ivf_ig_finish;
+ * b may exceed B.  The score is what ivf_i3d_backward differentiates (target [b]).  ig_map [b,T,HW], frames and
+ * abs_frames [b,T], total [b]; path_scores [b,K] (optional): the score at every path point; ws =
+ * ivf_ig_workspace_bytes(b, C, T, H*W, K) bytes from the caller, 256-byte aligned.  One stream, no host
+ * synchronisation, no allocation.  _ig_path_scores: forward only (stage -> forward -> pick), scores [b,K]; with
+ * alpha = {0} it scores the baseline itself. */
+int ivf_i3d_ig(ivf_i3d_t* net, const float* x, int b, const int* target, int base_kind, const float* base,
+               float base_value, const float* alpha, const float* w, int K, float* ig_map, float* frames,
+               float* abs_frames, float* total, float* path_scores, void* ws, ivf_stream_t stream);
+int ivf_i3d_ig_path_scores(ivf_i3d_t* net, const float* x, int b, const int* target, int base_kind, const float* base,
+                           float base_value, const float* alpha, int K, float* scores, ivf_stream_t stream);
+
 /* GradCamVideo.__call__ for archType "I3D" / target layer Mixed_5c,
  * grad_cam_videos.py:64-142, for b clips.  target[b] (device) selects the class;
  * cam [b,T'*(T/T'),out_h,out_w] (input_spatial_size, grad_cam_videos.py:54-57);
@@ -600,6 +640,19 @@ int ivf_clstm_blob_scores(ivf_clstm_t* net, const float* x, int b, const int* ta
  * exceed B.  One stream, no host synchronisation, no allocation. */
 int ivf_clstm_box_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W, int gh,
                       int gw, int max_len, int mh, int mw, float* scores, ivf_stream_t stream);
+
+/* Integrated Gradients of b clips through this plan (extension, see ivf_ig_*): the b*K path points run in chunks of the
+ * plan's B rows across clip boundaries (ivf_ig_stage -> forward -> backward -> ivf_ig_accumulate), then ivf_ig_finish;
+ * b may exceed B.  The score is what ivf_clstm_backward differentiates (target [b]).  ig_map [b,T,HW], frames and
+ * abs_frames [b,T], total [b]; path_scores [b,K] (optional): the score at every path point; ws =
+ * ivf_ig_workspace_bytes(b, C, T, H*W, K) bytes from the caller, 256-byte aligned.  One stream, no host
+ * synchronisation, no allocation.  _ig_path_scores: forward only (stage -> forward -> pick), scores [b,K]; with
+ * alpha = {0} it scores the baseline itself. */
+int ivf_clstm_ig(ivf_clstm_t* net, const float* x, int b, const int* target, int base_kind, const float* base,
+               float base_value, const float* alpha, const float* w, int K, float* ig_map, float* frames,
+               float* abs_frames, float* total, float* path_scores, void* ws, ivf_stream_t stream);
+int ivf_clstm_ig_path_scores(ivf_clstm_t* net, const float* x, int b, const int* target, int base_kind, const float* base,
+                           float base_value, const float* alpha, int K, float* scores, ivf_stream_t stream);
 
 /* Grad-CAM on the ConvLSTM's pooled layer outputs, stored [B,T,hid,plane] (plane = Hp*Wp), fp32:
  * weights[b,c] = mean over (selected steps, plane) of grad (grad_cam_videos.py:98), cam[b,e,:] =

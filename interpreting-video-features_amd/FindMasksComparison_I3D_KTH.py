@@ -19,7 +19,7 @@ _state = {"sub_dir": "run0"}
 
 def find_masks(dat_loader, model, config, lam1, lam2, N, ita=1, maskType="gradient", temporalMaskType="freeze",
                classOI=None, verbose=True, maxMaskLength=None, doGradCam=False, runTempMask=True, maskGrid=None,
-               maskSigma=None, lam3=None, maxBox=None):
+               maskSigma=None, lam3=None, maxBox=None, doIntGrad=False, igSteps=32, igBaseline="frozen"):
     """KTH:126-380.  maskType 'combi': the exhaustive one-blob search (KTH:138-142), masks of length <=
     maxMaskLength; 'spacetime' (an extension, no counterpart in the reference): a mask per frame and cell of a
     maskGrid (gh, gw) grid, blurred by maskSigma input pixels, lam3 on the spatial TV term, records with 'st_mask';
@@ -27,12 +27,15 @@ def find_masks(dat_loader, model, config, lam1, lam2, N, ita=1, maskType="gradie
     extension as well) is the exhaustive counterpart of 'spacetime': every box of one temporal blob (length <=
     maxMaskLength, default T) times one rectangle of at most maxBox = (mh, mw) grid cells (default the whole grid) is
     scored and the minimiser of the spacetime loss kept; N is unused; records also carry 'st_mask' (binary),
-    'box_start', 'box_length', 'box_rows', 'box_cols' and 'box_drop'."""
+    'box_start', 'box_length', 'box_rows', 'box_cols' and 'box_drop'.  doIntGrad (an extension as well, whatever the
+    maskType) also runs Integrated Gradients with igSteps midpoint nodes from the igBaseline ('frozen' or 'constant')
+    and writes a third pickle of records with 'IGHeatMap' [T,H,W], 'IGFrames' [T], 'ig_total', 'ig_gap', 'score_base'."""
     return ivf_find_masks.find_masks_impl(
         dat_loader, model, config, lam1, lam2, N, temporalMaskType, classOI, verbose, doGradCam, runTempMask,
         flavour="kth", sub_dir=_state["sub_dir"], gradcam_size=(RESIZE_SIZE_HEIGHT, RESIZE_SIZE_WIDTH),
         mask_mode=maskType if maskType in ("combi", "spacetime", "stcombi") else "central",
-        max_mask_length=maxMaskLength, mask_grid=maskGrid, mask_sigma=maskSigma, lam3=lam3, max_box=maxBox)
+        max_mask_length=maxMaskLength, mask_grid=maskGrid, mask_sigma=maskSigma, lam3=lam3, max_box=maxBox,
+        do_intgrad=doIntGrad, ig_steps=igSteps, ig_baseline=igBaseline)
 
 
 def build_model(config, args, device):

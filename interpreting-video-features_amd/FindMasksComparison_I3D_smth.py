@@ -23,7 +23,7 @@ _state = {"sub_dir": "run0"}
 
 def find_masks(dat_loader, model, hyper_params, lam1, lam2, N, maskType="gradient", temporalMaskType="freeze",
                classOI=None, verbose=True, maxMaskLength=None, doGradCam=False, runTempMask=True, maskGrid=None,
-               maskSigma=None, lam3=None, maxBox=None):
+               maskSigma=None, lam3=None, maxBox=None, doIntGrad=False, igSteps=32, igBaseline="frozen"):
     """smth:125-315.  maskType 'combi' runs the exhaustive one-blob search over masks of length <= maxMaskLength
     (smth:137-141, no gradient descent; N is unused); any other maskType keeps the gradient search from
     init_mask(mode="central"), which the reference hard-codes (smth:190).  maskType 'spacetime' (an extension, no
@@ -32,13 +32,16 @@ def find_masks(dat_loader, model, hyper_params, lam1, lam2, N, maskType="gradien
     extension as well) is the exhaustive counterpart of 'spacetime': every box of one temporal blob (length <=
     maxMaskLength, default T) times one rectangle of at most maxBox = (mh, mw) grid cells (default the whole grid) is
     scored and the minimiser of the spacetime loss kept; N is unused; records also carry 'st_mask' (binary),
-    'box_start', 'box_length', 'box_rows', 'box_cols' and 'box_drop'."""
+    'box_start', 'box_length', 'box_rows', 'box_cols' and 'box_drop'.  doIntGrad (an extension as well, whatever the
+    maskType) also runs Integrated Gradients with igSteps midpoint nodes from the igBaseline ('frozen' or 'constant')
+    and writes a third pickle of records with 'IGHeatMap' [T,H,W], 'IGFrames' [T], 'ig_total', 'ig_gap', 'score_base'."""
     return ivf_find_masks.find_masks_impl(
         dat_loader, model, hyper_params, lam1, lam2, N, temporalMaskType, classOI, verbose, doGradCam,
         runTempMask, flavour="smth", sub_dir=_state["sub_dir"],
         gradcam_size=(RESIZE_SIZE_HEIGHT, RESIZE_SIZE_WIDTH),
         mask_mode=maskType if maskType in ("combi", "spacetime", "stcombi") else "central",
-        max_mask_length=maxMaskLength, mask_grid=maskGrid, mask_sigma=maskSigma, lam3=lam3, max_box=maxBox)
+        max_mask_length=maxMaskLength, mask_grid=maskGrid, mask_sigma=maskSigma, lam3=lam3, max_box=maxBox,
+        do_intgrad=doIntGrad, ig_steps=igSteps, ig_baseline=igBaseline)
 
 
 def main(argv=None):

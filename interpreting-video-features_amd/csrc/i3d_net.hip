@@ -894,6 +894,31 @@ extern "C" int ivf_i3d_box_scores(ivf_i3d_t* net, const float* x, int b, const i
                         (hipStream_t)stream);
 }
 
+// Integrated Gradients (ig_ops.hip): run_ig / run_ig_path_scores on this plan; scratch from the caller.
+extern "C" int ivf_i3d_ig(ivf_i3d_t* net, const float* x, int b, const int* target, int base_kind, const float* base,
+                          float base_value, const float* alpha, const float* w, int K, float* ig_map, float* frames,
+                          float* abs_frames, float* total, float* path_scores, void* ws, ivf_stream_t stream) {
+  IVF_PROPAGATE(check_ready(net, 1));
+  IVF_CHECK_ARG(x && target && alpha && w && ig_map && frames && abs_frames && total && ws, "i3d_ig: null pointer");
+  IVF_CHECK_ARG(b > 0 && K > 0, "i3d_ig: bad batch %d or node count %d", b, K);
+  IVF_CHECK_ARG(base_kind == 0 || base_kind == 1 || (base_kind == 2 && base),
+                "i3d_ig: base_kind must be 0 (frozen), 1 (constant) or 2 (clip, base given)");
+  return run_ig(backbone(net), x, b, target, base_kind, base, base_value, alpha, w, K, ig_map, frames, abs_frames, total,
+                path_scores, ws, (hipStream_t)stream);
+}
+
+extern "C" int ivf_i3d_ig_path_scores(ivf_i3d_t* net, const float* x, int b, const int* target, int base_kind,
+                                      const float* base, float base_value, const float* alpha, int K, float* scores,
+                                      ivf_stream_t stream) {
+  IVF_PROPAGATE(check_ready(net, 1));
+  IVF_CHECK_ARG(x && target && alpha && scores, "i3d_ig_path_scores: null pointer");
+  IVF_CHECK_ARG(b > 0 && K > 0, "i3d_ig_path_scores: bad batch %d or node count %d", b, K);
+  IVF_CHECK_ARG(base_kind == 0 || base_kind == 1 || (base_kind == 2 && base),
+                "i3d_ig_path_scores: base_kind must be 0 (frozen), 1 (constant) or 2 (clip, base given)");
+  return run_ig_path_scores(backbone(net), x, b, target, base_kind, base, base_value, alpha, K, scores,
+                            (hipStream_t)stream);
+}
+
 extern "C" int ivf_i3d_gradcam(ivf_i3d_t* net, const float* x, int b, const int* target, int per_frame,
                                int out_h, int out_w, float* cam, float* probs, ivf_stream_t stream) {
   IVF_PROPAGATE(check_ready(net, b));

@@ -23,6 +23,9 @@ void prof_name(int variant, const char* fmt, ...);   // kernel name of a profile
 int blob_pick(const float* probs, const int* target, int K, int n, long long first, int count, float* scores,
               hipStream_t s);
 
+// Integrated Gradients (ig_ops.hip): rowt[g] = target[g / K] for the b * K rows of the (clip, node) list
+int ig_row_targets(const int* target, int b, int K, int* rowt, hipStream_t s);
+
 // index k of the canonical one-blob order (length ascending, then start) on an axis of T positions -> (start, length);
 // the three axes of the one-box search (stmask_ops.hip) decode with it as well
 __device__ __forceinline__ void blob_decode(int k, int T, int* a, int* L) {

@@ -193,4 +193,65 @@ static inline int run_box_scores(const Backbone& v, const float* x, int b, const
   return IVF_OK;
 }
 
+// ---------------------------------------------------------------- Integrated Gradients (ig_ops.hip)
+// An extension without a counterpart in the reference.  Its scratch belongs to the CALLER (ivf_ig_workspace_bytes), so
+// no plan's workspace size or carve order moves.
+struct IgScratch {
+  size_t gsum = 0, rowt = 0, score = 0;
+
+  // byte offsets of the pieces, each 256-byte aligned; returns the total.  per_clip = C * T * HW.
+  size_t carve(size_t b, size_t per_clip, size_t K) {
+    size_t top = 0;
+    auto take = [&top](size_t bytes) {
+      size_t off = top;
+      top += align_up(bytes, 256);
+      return off;
+    };
+    gsum = take(b * per_clip * 4);
+    rowt = take(b * K * 4);
+    score = take(b * K * 4);
+    return top;
+  }
+};
+
+// Scores of the b * K path points x0 + alpha[k] (x - x0), as run_blob_scores runs its candidates: chunks of the plan's B
+// rows across clip boundaries, ivf_ig_stage -> forward -> blob_pick.  scores [b,K].
+static inline int run_ig_path_scores(const Backbone& v, const float* x, int b, const int* target, int base_kind,
+                                     const float* base, float base_value, const float* alpha, int K, float* scores,
+                                     hipStream_t s) {
+  const long long total = (long long)b * K;
+  for (long long first = 0; first < total; first += v.B) {
+    const int cnt = (int)std::min<long long>(v.B, total - first);
+    IVF_PROPAGATE(ivf_ig_stage(x, base_kind, base, base_value, alpha, b, v.C, v.T, v.HW, K, first, cnt, v.in, v.layout, s));
+    IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
+    IVF_PROPAGATE(blob_pick(v.probs, target, v.K, K, first, cnt, scores, s));
+  }
+  return IVF_OK;
+}
+
+// Integrated Gradients of b clips: per chunk of the plan's B rows stage -> forward -> backward -> accumulate, then
+// finish.  path_scores [b,K] (optional): the scores the backward writes.  `ws`: the caller's
+// ivf_ig_workspace_bytes(b, C, T, HW, K) bytes.  One stream, no host synchronisation, no allocation.
+static int run_ig(const Backbone& v, const float* x, int b, const int* target, int base_kind, const float* base,
+                  float base_value, const float* alpha, const float* w, int K, float* ig_map, float* frames,
+                  float* abs_frames, float* total_out, float* path_scores, void* ws, hipStream_t s) {
+  IgScratch c;
+  const size_t per_clip = (size_t)v.C * v.T * v.HW;
+  c.carve((size_t)b, per_clip, (size_t)K);
+  float* Gsum = (float*)((char*)ws + c.gsum);
+  int* rowt = (int*)((char*)ws + c.rowt);
+  float* score = path_scores ? path_scores : (float*)((char*)ws + c.score);
+  IVF_CHECK_HIP(hipMemsetAsync(Gsum, 0, (size_t)b * per_clip * 4, s));
+  IVF_PROPAGATE(ig_row_targets(target, b, K, rowt, s));
+  const long long total = (long long)b * K;
+  for (long long first = 0; first < total; first += v.B) {
+    const int cnt = (int)std::min<long long>(v.B, total - first);
+    IVF_PROPAGATE(ivf_ig_stage(x, base_kind, base, base_value, alpha, b, v.C, v.T, v.HW, K, first, cnt, v.in, v.layout, s));
+    IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
+    IVF_PROPAGATE(v.backward(v.plan, cnt, rowt + first, score + first, s));
+    IVF_PROPAGATE(ivf_ig_accumulate(v.din, v.layout, w, K, first, cnt, Gsum, b, v.C, v.T, v.HW, s));
+  }
+  return ivf_ig_finish(x, base_kind, base, base_value, Gsum, b, v.C, v.T, v.HW, ig_map, frames, abs_frames, total_out, s);
+}
+
 }  // namespace ivf

@@ -291,6 +291,102 @@ class _Engine:
                                            L.ptr(scores), L.stream()))
         return scores
 
+    # -------------------------------------------------------------- Integrated Gradients (extension)
+    _has_ig = True          # ivf_<prefix>_ig / _ig_path_scores exist (not for the TF plan)
+
+    def _ig_args(self, x, baseline, base):
+        """(base_kind, base tensor or None, base_value) of a baseline: 'frozen' (frame 0 of the row's own clip at every
+        frame), 'constant' (base: one value, default 0.0 = black) or 'clip' (base: a [b,C,T,H,W] tensor)."""
+        if not self._has_ig:
+            raise L.IvfError("Integrated Gradients is built for the I3D and CLSTM plans only")
+        if baseline == "frozen":
+            if base is not None:
+                raise L.IvfError("baseline 'frozen' takes no base")
+            return 0, None, 0.0
+        if baseline == "constant":
+            return 1, None, 0.0 if base is None else float(base)
+        if baseline == "clip":
+            if base is None:
+                raise L.IvfError("baseline 'clip' needs base, a [b,C,T,H,W] tensor")
+            L.require_gpu(base)
+            base = L.f32c(base)
+            if tuple(base.shape) != tuple(x.shape):
+                raise L.IvfError(f"base must be {tuple(x.shape)}, got {tuple(base.shape)}")
+            return 2, base, 0.0
+        raise L.IvfError(f"baseline must be 'frozen', 'constant' or 'clip', got {baseline!r}")
+
+    def _ig_rule(self, steps, alpha, weights, need_weights=True):
+        """(K, alpha [K], w [K]) on the device, built on the host in fp32.  Default: the midpoint rule,
+        alpha_k = (2k+1)/(2K), w_k = 1/K.  need_weights=False (forward only): w is None unless given."""
+        if alpha is None:
+            K = int(steps)
+            if K < 1:
+                raise L.IvfError(f"steps must be >= 1, got {steps}")
+            alpha = (2.0 * np.arange(K, dtype=np.float32) + np.float32(1.0)) / np.float32(2 * K)
+            if weights is None:
+                weights = np.full(K, np.float32(1.0) / np.float32(K), dtype=np.float32)
+        alpha = np.ascontiguousarray(np.asarray(alpha, dtype=np.float32).reshape(-1))
+        K = alpha.size
+        if K < 1:
+            raise L.IvfError("alpha must hold at least one node")
+        if weights is None:
+            if need_weights:
+                raise L.IvfError("explicit alpha needs explicit weights")
+            return K, torch.from_numpy(alpha).to(self.device), None
+        weights = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+        if weights.size != K:
+            raise L.IvfError(f"need {K} weights, got {weights.size}")
+        return K, torch.from_numpy(alpha).to(self.device), torch.from_numpy(weights).to(self.device)
+
+    def ig_path_scores(self, x, target, baseline="frozen", base=None, alpha=None, steps=32):
+        """Scores [b,K] of target[clip] at the path points x0 + alpha[k] (x - x0) (ivf_*_ig_path_scores: forward only,
+        chunks of the plan's max_batch rows; b may exceed max_batch).  alpha=[0] scores the baseline itself."""
+        x = self._clip(x, any_batch=True)
+        b = x.shape[0]
+        kind, base, value = self._ig_args(x, baseline, base)
+        K, a, _ = self._ig_rule(steps, alpha, None, need_weights=False)
+        tgt = self._targets(target, b)
+        scores = torch.empty(b, K, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(self._fn("ig_path_scores")(self._h, L.ptr(x), b, L.ptr(tgt), kind, L.ptr(base), value, L.ptr(a), K,
+                                               L.ptr(scores), L.stream()))
+        return scores
+
+    def ig(self, x, target, steps=32, baseline="frozen", base=None, alpha=None, weights=None):
+        """Integrated Gradients of target[clip] on b clips (ivf_*_ig; b may exceed max_batch).  Returns a dict of
+        device tensors: ig_map [b,T,H,W], ig_frames, ig_abs_frames [b,T], ig_total [b], path_scores [b,K], score_x,
+        score_base [b] and ig_gap = ig_total - (score_x - score_base), the quadrature error to choose `steps` by.
+        score_base is the forward-only entry at alpha = [0] (the baseline staged exactly), score_x the plan's
+        ordinary forward."""
+        x = self._clip(x, any_batch=True)
+        b = x.shape[0]
+        C, T, H, W = self.clip_shape
+        base_arg = base
+        kind, base, value = self._ig_args(x, baseline, base)
+        K, a, w = self._ig_rule(steps, alpha, weights)
+        tgt = self._targets(target, b)
+        nbytes = L.lib().ivf_ig_workspace_bytes(b, C, T, H * W, K)
+        if nbytes == 0:
+            raise L.IvfError(L.lib().ivf_last_error().decode())
+        ws = self.__dict__.get("_ig_ws")
+        if ws is None or ws.numel() < nbytes:
+            with torch.cuda.device(self.device):
+                ws = self._ig_ws = _arena(nbytes, self.device)
+        dev = self.device
+        out = dict(ig_map=torch.empty(b, T, H, W, device=dev), ig_frames=torch.empty(b, T, device=dev),
+                   ig_abs_frames=torch.empty(b, T, device=dev), ig_total=torch.empty(b, device=dev),
+                   path_scores=torch.empty(b, K, device=dev))
+        with torch.cuda.device(dev):
+            L.check(self._fn("ig")(self._h, L.ptr(x), b, L.ptr(tgt), kind, L.ptr(base), value, L.ptr(a), L.ptr(w), K,
+                                   L.ptr(out["ig_map"]), L.ptr(out["ig_frames"]), L.ptr(out["ig_abs_frames"]),
+                                   L.ptr(out["ig_total"]), L.ptr(out["path_scores"]), L.ptr(ws), L.stream()))
+        out["score_base"] = self.ig_path_scores(x, tgt, baseline, base_arg, alpha=[0.0])[:, 0]
+        idx = tgt.long().view(-1, 1)
+        out["score_x"] = torch.cat([self.forward(x[i:i + self.max_batch]).gather(1, idx[i:i + self.max_batch])
+                                    for i in range(0, b, self.max_batch)])[:, 0]
+        out["ig_gap"] = out["ig_total"] - (out["score_x"] - out["score_base"])
+        return out
+
     def argmax(self, probs):
         b = probs.shape[0]
         t = torch.empty(b, dtype=torch.int32, device=self.device)
@@ -551,10 +647,12 @@ class TFCLSTMEngine(_Engine):
     (video_features_tf/models/clstm.py:87-126) and its temporal-mask search / per-frame Grad-CAM
     (mask/find_mask_kth.py:300-452, mask/gradcam.py:28-111) on libivf_hip's generic direct-convolution kernels
     (csrc/tf_clstm.hip).  Clips are NCTHW like everywhere else; `from_tf_layout` converts [B,T,H,W,C].
-    The plan perturbs by freezing only and has no one-blob entry (the inherited `blob_scores` finds no symbol)."""
+    The plan perturbs by freezing only and has no one-blob entry (the inherited `blob_scores` finds no symbol); `ig`
+    and `ig_path_scores` refuse with IvfError."""
     _prefix = "tfclstm"
     _has_mode = False
     _has_st = False
+    _has_ig = False
 
     def __init__(self, num_classes, clip_shape, units=(32, 32), kernel=(3, 5), stride=2, padding="valid",
                  recurrent_activation="hard_sigmoid", only_last_element_for_fc=True, max_batch=1, device=None):

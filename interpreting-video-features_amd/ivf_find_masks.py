@@ -47,8 +47,13 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                     verbose=True, doGradCam=False, runTempMask=True, flavour="smth", sub_dir="run0",
                     results_path="results/", gradcam_size=None, write_files=True, device=None, visualise=True,
                     mask_mode="central", max_mask_length=None, blob_batch=32, mask_grid=None, mask_sigma=None, lam3=None,
-                    max_box=None):
-    """mask_mode 'stcombi' (the drivers' maskType='stcombi', an extension: DESIGN 12) scores every one-box space-time
+                    max_box=None, do_intgrad=False, ig_steps=32, ig_baseline="frozen"):
+    """do_intgrad (the drivers' doIntGrad, an extension: DESIGN 13) also runs Integrated Gradients of the target's score
+    (ig_steps midpoint nodes from ig_baseline 'frozen' or 'constant') and writes a third list of records -- true_class,
+    pred_class, video_id, IGHeatMap [T,H,W], IGFrames [T], ig_total, ig_gap, score_base -- to a third pickle named like
+    the Grad-CAM one with IntGrad in place of GradCam; with the strips on, a second set of heat-map strips (folder
+    `intgrad` beside `combined`) blends max(ig_map, 0) normalised per frame.  Off, nothing changes.
+    mask_mode 'stcombi' (the drivers' maskType='stcombi', an extension: DESIGN 12) scores every one-box space-time
     mask (one temporal blob of length <= max_mask_length times one rectangle of at most max_box grid cells) and keeps the
     minimiser of the spacetime loss; its plan holds at least blob_batch clips, its records also carry st_mask (binary),
     box_start, box_length, box_rows (i0, bh), box_cols (j0, bw) and box_drop [T,gh,gw], and the strips and PNGs are
@@ -63,7 +68,7 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
     net = _unwrap(model)
     net.eval()                                                      # smth:145
     flt = _class_filter(classOI)
-    masks, time_results, cam_results = [], [], []
+    masks, time_results, cam_results, ig_results = [], [], [], []
     if write_files and not os.path.exists(results_path):
         os.makedirs(results_path)
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -87,15 +92,25 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                        do_gradcam=doGradCam, run_temp_mask=runTempMask,
                                        normalize_per_frame=True, gradcam_size=gradcam_size, mask_mode=mask_mode,
                                        max_mask_length=max_mask_length, mask_grid=mask_grid, mask_sigma=mask_sigma,
-                                       lam3=lam3, max_box=max_box)
+                                       lam3=lam3, max_box=max_box, do_intgrad=do_intgrad, ig_steps=ig_steps,
+                                       ig_baseline=ig_baseline)
         res = search.run(xs, labels[keep])
-        host = {k: v.detach().cpu() for k, v in res.items() if k not in ("gradcam", "box_scores")}
+        host = {k: v.detach().cpu() for k, v in res.items() if k not in ("gradcam", "box_scores", "ig_map")}
         spacetime = runTempMask and mask_mode in ("spacetime", "stcombi")
         st_maps = eng.st_expand(res["st_mask"], search.st_grid(xs), mask_sigma) if spacetime and write_files and visualise \
             else None
         st_pert = eng.st_freeze(xs, st_maps) if st_maps is not None and flavour != "smth" else None   # what was searched
         if doGradCam:
             host["gradcam"] = res["gradcam"].detach().cpu()
+        ig_heat = None
+        if do_intgrad:
+            host["ig_map"] = res["ig_map"].detach().cpu()
+            if runTempMask and write_files and visualise:
+                # max(ig_map, 0) scaled to [0,1] per frame, the range ivf_viz_blend takes; a frame without a positive
+                # attribution (frame 0 under 'frozen') stays all zero
+                pos = res["ig_map"].clamp_min(0.0)
+                top = pos.amax(dim=(2, 3), keepdim=True)
+                ig_heat = torch.where(top > 0, pos / torch.where(top > 0, top, torch.ones_like(top)), torch.zeros_like(pos))
         for j, bi in enumerate(keep):
             true_class = int(labels[bi])
             pred = int(host["pred_class"][j])
@@ -134,6 +149,13 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                 cam_results.append({'true_class': true_class, 'pred_class': pred,
                                     'video_id': int(vid) if flavour == "smth" else vid,
                                     'GCHeatMap': host["gradcam"][j].numpy().astype(np.float32)})
+            if do_intgrad:
+                ig_results.append({'true_class': true_class, 'pred_class': pred,
+                                   'video_id': int(vid) if flavour == "smth" else vid,
+                                   'IGHeatMap': host["ig_map"][j].numpy().astype(np.float32),
+                                   'IGFrames': host["ig_frames"][j].numpy().astype(np.float32),
+                                   'ig_total': float(host["ig_total"][j]), 'ig_gap': float(host["ig_gap"][j]),
+                                   'score_base': float(host["ig_score_base"][j])})
             if runTempMask and write_files and visualise:
                 # smth:296-303 / KTH:354-367: heat-map strips with the mask dot row for both perturbation
                 # types (the dot row snaps a host copy: `tmask` keeps its sigmoid values, as the reference's
@@ -143,6 +165,10 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                     heat = st_maps[j] if st_maps is not None else res["gradcam"][j]
                     for kind in ("freeze", "reverse"):
                         viz.create_image_arrays(xs, heat, tmask, j, kind, d, str(vid), 0, xs.shape[4], xs.shape[3])
+                if ig_heat is not None:
+                    for kind in ("freeze", "reverse"):
+                        viz.create_image_arrays(xs, ig_heat[j], tmask, j, kind, os.path.join(os.path.dirname(d), "intgrad"),
+                                                str(vid), 0, xs.shape[4], xs.shape[3])
                 if flavour != "smth":
                     import mask as _mask
                     pert = st_pert[j] if st_pert is not None else _mask.perturb_sequence(xs, tmask, temporalMaskType)[j]
@@ -162,7 +188,11 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
             pickle.dump(time_results, f)
         with open(os.path.join(results_path, gname.replace(os.sep, "_")), "wb") as f:
             pickle.dump(cam_results, f)
+        if do_intgrad:
+            with open(os.path.join(results_path, gname.replace("GradCam", "IntGrad").replace(os.sep, "_")), "wb") as f:
+                pickle.dump(ig_results, f)
     find_masks_impl.last_results = (time_results, cam_results)
+    find_masks_impl.last_ig_results = ig_results
     return masks
 
 

@@ -4,6 +4,7 @@ The HIP library IS the product: if it is missing or a call fails this module
 raises -- there is no CPU or PyTorch fallback anywhere in the package.
 PyTorch is used only for device memory and streams.
 """
+import collections
 import ctypes
 import os
 from ctypes import (POINTER, Structure, byref, c_char, c_char_p, c_float, c_int,
@@ -99,6 +100,11 @@ _SIGS = {
     "ivf_box_stage": (c_int, [_P] + [_I] * 5 + [_P, _P] + [_I] * 5 + [ctypes.c_longlong, _I, _P, _I, _P]),
     "ivf_box_select": (c_int, [_P, _P, _P] + [_I] * 7 + [_F] * 4 + [_P] * 5),
     "ivf_box_drop": (c_int, [_P, _P] + [_I] * 7 + [_P, _P]),
+    # csrc/ig_ops.hip (Integrated Gradients, documented extension)
+    "ivf_ig_stage": (c_int, [_P, _I, _P, _F, _P] + [_I] * 5 + [ctypes.c_longlong, _I, _P, _I, _P]),
+    "ivf_ig_accumulate": (c_int, [_P, _I, _P, _I, ctypes.c_longlong, _I, _P] + [_I] * 4 + [_P]),
+    "ivf_ig_finish": (c_int, [_P, _I, _P, _F, _P] + [_I] * 4 + [_P] * 5),
+    "ivf_ig_workspace_bytes": (c_size_t, [_I] * 5),
     "ivf_clip_ingest_u8": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ivf_conv3d": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
     "ivf_bn_fold": (c_int, [_P, _P, _P, _P, _F, _P, _P, _I, _P]),
@@ -140,6 +146,8 @@ _SIGS = {
     "ivf_i3d_stsearch": (c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I] + [_F] * 7 + [_I, _I, _P, _P, _P]),
     "ivf_i3d_stperturbed_forward": (c_int, [_P, _P, _I, _P, _P, _P]),
     "ivf_i3d_blob_scores": (c_int, [_P, _P, _I, _P, _I, _I, _P, _P]),
+    "ivf_i3d_ig": (c_int, [_P, _P, _I, _P, _I, _P, _F, _P, _P, _I] + [_P] * 7),
+    "ivf_i3d_ig_path_scores": (c_int, [_P, _P, _I, _P, _I, _P, _F, _P, _I, _P, _P]),
     "ivf_i3d_box_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 5 + [_P, _P]),
     "ivf_i3d_gradcam": (c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "ivf_i3d_gradcam_layer": (c_int, [_P, _P, _I, _P, c_char_p, _I, _I, _I, _P, _P, _P]),
@@ -176,6 +184,8 @@ _SIGS = {
     "ivf_clstm_stsearch": (c_int, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I] + [_F] * 7 + [_I, _I, _P, _P, _P]),
     "ivf_clstm_stperturbed_forward": (c_int, [_P, _P, _I, _P, _P, _P]),
     "ivf_clstm_blob_scores": (c_int, [_P, _P, _I, _P, _I, _I, _P, _P]),
+    "ivf_clstm_ig": (c_int, [_P, _P, _I, _P, _I, _P, _F, _P, _P, _I] + [_P] * 7),
+    "ivf_clstm_ig_path_scores": (c_int, [_P, _P, _I, _P, _I, _P, _F, _P, _I, _P, _P]),
     "ivf_clstm_box_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 5 + [_P, _P]),
     "ivf_clstm_gradcam_reduce": (c_int, [_P, _P, POINTER(c_int), _I, _P, _P, _I, _I, _I, _I, _P]),
     "ivf_clstm_set_cam_steps": (c_int, [_P, POINTER(c_int), _I]),
@@ -231,10 +241,17 @@ def check(rc):
         raise IvfError(f"libivf_hip error {rc}: {lib().ivf_last_error().decode()}")
 
 
+_recent = collections.deque(maxlen=64)
+
+
 def ptr(t):
-    """Device pointer of a tensor (None -> NULL)."""
+    """Device pointer of a tensor (None -> NULL).  The tensor stays referenced for the next 64 pointers taken: a
+    temporary passed as `ptr(x.cuda())` would otherwise hand its block back to the caching allocator before the other
+    arguments of the same call are built, and a tensor created for one of them could be placed on it and overwrite it
+    before the kernel runs."""
     if t is None:
         return None
+    _recent.append(t)
     return c_void_p(t.data_ptr())
 
 

@@ -213,8 +213,13 @@ class MaskSearch:
     def __init__(self, engine, lam1=0.01, lam2=0.02, n_iter=300, mask_type="freeze", threshold=0.9,
                  lr=0.2, grad_cam_type="guessed", do_gradcam=True, run_temp_mask=True,
                  normalize_per_frame=True, gradcam_size=None, mask_mode="central", max_mask_length=None,
-                 mask_grid=None, mask_sigma=None, lam3=None, max_box=None):
-        """mask_mode 'central': init_mask('central') + n_iter Adam steps (smth:188-214); 'combi': the exhaustive
+                 mask_grid=None, mask_sigma=None, lam3=None, max_box=None, do_intgrad=False, ig_steps=32,
+                 ig_baseline="frozen"):
+        """do_intgrad (an extension without a counterpart in the reference): also run Integrated Gradients
+        of the target's score with ig_steps midpoint nodes from the ig_baseline ('frozen': every frame = frame 0, the
+        fully frozen clip of mask.py:123-128; 'constant': black); run() then also returns ig_map [b,T,H,W], ig_frames
+        [b,T], ig_abs_frames, ig_total, ig_gap and ig_score_base [b].
+        mask_mode 'central': init_mask('central') + n_iter Adam steps (smth:188-214); 'combi': the exhaustive
         one-blob search (smth:137-141) over masks of length <= max_mask_length (default T), no gradient descent;
         'spacetime' (an extension without a counterpart in the reference): the gradient search on a mask per
         frame and grid cell -- mask_grid (gh, gw) (default one cell per 32 input pixels: 7x7 at 224^2, 4x5 at
@@ -236,6 +241,9 @@ class MaskSearch:
         self.do_gradcam, self.run_temp_mask = do_gradcam, run_temp_mask
         self.normalize_per_frame = normalize_per_frame
         self.gradcam_size = gradcam_size
+        self.do_intgrad, self.ig_steps, self.ig_baseline = bool(do_intgrad), ig_steps, ig_baseline   # read only when on
+        if self.do_intgrad and ig_baseline not in ("frozen", "constant"):
+            raise L.IvfError(f"ig_baseline must be 'frozen' or 'constant', got {ig_baseline!r}")
 
     def run(self, x, labels, want_traj=False):
         """x [b,C,T,H,W] float32 on the GPU, labels [b] ints.  Returns a dict of device
@@ -280,6 +288,11 @@ class MaskSearch:
             gc_target = pred if self.grad_cam_type == "guessed" else target  # smth:253,266-267
             cam, _ = eng.gradcam(x, gc_target, per_frame=self.normalize_per_frame, out_hw=self.gradcam_size)
             out["gradcam"] = cam                                             # smth:269
+        if self.do_intgrad:
+            r = eng.ig(x, target, steps=self.ig_steps, baseline=self.ig_baseline)
+            for k in ("ig_map", "ig_frames", "ig_abs_frames", "ig_total", "ig_gap"):
+                out[k] = r[k]
+            out["ig_score_base"] = r["score_base"]
         return out
 
 
