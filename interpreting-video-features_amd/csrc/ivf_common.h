@@ -1,13 +1,19 @@
 // Shared host-side helpers for libivf_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/ivf_hip.h"
 
 namespace ivf {
+
+// most frames of a mask: the freeze backward kernels keep a pixel's frames in registers, the regularisers a row in
+// a thread's private arrays
+constexpr int MAX_T = 64;
 
 void set_error(const char* fmt, ...);
 
@@ -18,6 +24,11 @@ void prof_set_site(int site);   // launch site of the next sampled launches (2 *
 bool prof_begin(hipStream_t s, int variant);
 void prof_end(hipStream_t s);
 void prof_name(int variant, const char* fmt, ...);   // kernel name of a profiler class (first call wins)
+
+// freeze scan (mask_ops.hip) behind ivf_freeze_fwd and ivf_stfreeze_fwd, arguments checked by them: `mask` holds one
+// value per frame ([B,T], or [T] with mask_per_clip == 0) or, with pixel_mask, one per frame and pixel ([B,T,HW])
+int freeze_fwd(const float* x, const float* mask, bool pixel_mask, float* p, int B, int C, int T, int HW,
+               int mask_per_clip, int out_cpad, hipStream_t s);
 
 // one-blob search (mask_ops.hip): scores[first + j] = probs[j][target[(first + j) / n]] for the `count` rows of a chunk
 int blob_pick(const float* probs, const int* target, int K, int n, long long first, int count, float* scores,
@@ -91,6 +102,30 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 static inline int grid_for(size_t total, int block = 256, int cap = 4096) {
   size_t g = (total + block - 1) / block;
   return (int)(g > (size_t)cap ? cap : (g ? g : 1));
+}
+
+// Frame count as a compile-time constant, in the manner of with_const_1to4 (convlstm.hip): f(integral_constant<int, TT>).
+// exact: TT == T for the two clip lengths whose forward scans are unrolled, else 0 (the run-time loop, any T).
+template <class F>
+static inline void with_frames_exact(int T, F&& f) {
+  if (T == 16) f(std::integral_constant<int, 16>{});
+  else if (T == 32) f(std::integral_constant<int, 32>{});
+  else f(std::integral_constant<int, 0>{});
+}
+// upto: the smallest TT of 16, 32, MAX_T with T <= TT (register arrays of the backward scans)
+template <class F>
+static inline void with_frames_upto(int T, F&& f) {
+  if (T <= 16) f(std::integral_constant<int, 16>{});
+  else if (T <= 32) f(std::integral_constant<int, 32>{});
+  else f(std::integral_constant<int, MAX_T>{});
+}
+
+// torch.optim.Adam's bias corrections of step `step`, in double as torch computes them
+static inline void adam_coeffs(int step, float lr, float b1, float b2, float* step_size, float* inv_sqrt_bc2) {
+  double bc1 = 1.0 - pow((double)b1, step);
+  double bc2 = 1.0 - pow((double)b2, step);
+  *step_size = (float)((double)lr / bc1);
+  *inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
 }
 
 // TF-'same' front padding along one dim (reference I3D_doubled.py:9-13, 29-34).

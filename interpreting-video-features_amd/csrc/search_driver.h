@@ -96,6 +96,26 @@ static int run_search(const Backbone& v, const float* x, int b, const int* targe
   return IVF_OK;
 }
 
+// Caller-owned scratch (StScratch, IgScratch below): byte offsets handed out in call order, each piece rounded up to
+// 256 bytes; `top` is the total.  The order and the sizes of the calls are part of the ABI (ivf_*_workspace_bytes).
+struct Bump256 {
+  size_t top = 0;
+  size_t take(size_t bytes) {
+    size_t off = top;
+    top += align_up(bytes, 256);
+    return off;
+  }
+};
+
+// The `total` rows of a flattened candidate list in chunks of the plan's B rows (chunks cross clip boundaries, so one
+// clip still fills the plan): body(first, cnt) per chunk, the first non-OK code ends the loop.
+template <class Body>
+static inline int for_each_chunk(const Backbone& v, long long total, Body&& body) {
+  for (long long first = 0; first < total; first += v.B)
+    IVF_PROPAGATE(body(first, (int)std::min<long long>(v.B, total - first)));
+  return IVF_OK;
+}
+
 // ---------------------------------------------------------------- spatio-temporal masks (maskType 'spacetime')
 // An extension without a counterpart in the reference (stmask_ops.hip).  Its scratch belongs to the CALLER
 // (ivf_stsearch_workspace_bytes), so no plan's workspace size or carve order moves.
@@ -104,20 +124,15 @@ struct StScratch {
 
   // byte offsets of the pieces, each 256-byte aligned; returns the total
   size_t carve(size_t B, size_t T, size_t HW, size_t cells) {
-    size_t top = 0;
-    auto take = [&top](size_t bytes) {
-      size_t off = top;
-      top += align_up(bytes, 256);
-      return off;
-    };
-    M = take(B * T * HW * 4);
-    dM = take(B * T * HW * 4);
-    sig = take(B * T * cells * 4);
-    dreg = take(B * T * cells * 4);
-    dsig = take(B * T * cells * 4);
-    terms = take(B * 3 * 4);
-    score = take(B * 4);
-    return top;
+    Bump256 a;
+    M = a.take(B * T * HW * 4);
+    dM = a.take(B * T * HW * 4);
+    sig = a.take(B * T * cells * 4);
+    dreg = a.take(B * T * cells * 4);
+    dsig = a.take(B * T * cells * 4);
+    terms = a.take(B * 3 * 4);
+    score = a.take(B * 4);
+    return a.top;
   }
 };
 
@@ -158,39 +173,32 @@ static int run_st_search(const Backbone& v, const float* x, int b, const int* ta
   return IVF_OK;
 }
 
-// Exhaustive one-blob search (maskType 'combi'): the b*n candidates of b clips run in chunks of the plan's B rows --
+// Exhaustive one-blob search (maskType 'combi'): the b*n candidates of b clips run in chunks (for_each_chunk) --
 // stage straight into the input buffer, forward, pick the target score -- all on one stream, no host sync, no
-// allocation.  Chunks cross clip boundaries, so one clip still fills the plan.
+// allocation.
 static inline int run_blob_scores(const Backbone& v, const float* x, int b, const int* target, int max_len, int mode,
                                   float* scores, hipStream_t s) {
   const int n = ivf_blob_count(v.T, max_len);
   if (n < 0) return IVF_ERR_BAD_ARG;
-  const long long total = (long long)b * n;
-  for (long long first = 0; first < total; first += v.B) {
-    const int cnt = (int)std::min<long long>(v.B, total - first);
+  return for_each_chunk(v, (long long)b * n, [&](long long first, int cnt) -> int {
     IVF_PROPAGATE(ivf_blob_stage(x, b, v.C, v.T, v.HW, max_len, mode, first, cnt, v.in, v.layout, s));
     IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
-    IVF_PROPAGATE(blob_pick(v.probs, target, v.K, n, first, cnt, scores, s));
-  }
-  return IVF_OK;
+    return blob_pick(v.probs, target, v.K, n, first, cnt, scores, s);
+  });
 }
 
-// Exhaustive one-box search (maskType 'stcombi', stmask_ops.hip): run_blob_scores with the box staging -- the b*n
-// candidates in chunks of the plan's B rows across clip boundaries, ivf_box_stage -> forward -> blob_pick, one stream,
-// no host synchronisation, no allocation.
+// Exhaustive one-box search (maskType 'stcombi', stmask_ops.hip): run_blob_scores with the box staging -- per chunk
+// ivf_box_stage -> forward -> blob_pick, one stream, no host synchronisation, no allocation.
 static inline int run_box_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,
                                  const float* A_W, int gh, int gw, int H, int W, int max_len, int mh, int mw,
                                  float* scores, hipStream_t s) {
   const long long n = ivf_box_count(v.T, max_len, gh, gw, mh, mw);
   if (n < 0) return IVF_ERR_BAD_ARG;
-  const long long total = (long long)b * n;
-  for (long long first = 0; first < total; first += v.B) {
-    const int cnt = (int)std::min<long long>(v.B, total - first);
+  return for_each_chunk(v, (long long)b * n, [&](long long first, int cnt) -> int {
     IVF_PROPAGATE(ivf_box_stage(x, b, v.C, v.T, H, W, A_H, A_W, gh, gw, max_len, mh, mw, first, cnt, v.in, v.layout, s));
     IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
-    IVF_PROPAGATE(blob_pick(v.probs, target, v.K, (int)n, first, cnt, scores, s));
-  }
-  return IVF_OK;
+    return blob_pick(v.probs, target, v.K, (int)n, first, cnt, scores, s);
+  });
 }
 
 // ---------------------------------------------------------------- Integrated Gradients (ig_ops.hip)
@@ -201,32 +209,24 @@ struct IgScratch {
 
   // byte offsets of the pieces, each 256-byte aligned; returns the total.  per_clip = C * T * HW.
   size_t carve(size_t b, size_t per_clip, size_t K) {
-    size_t top = 0;
-    auto take = [&top](size_t bytes) {
-      size_t off = top;
-      top += align_up(bytes, 256);
-      return off;
-    };
-    gsum = take(b * per_clip * 4);
-    rowt = take(b * K * 4);
-    score = take(b * K * 4);
-    return top;
+    Bump256 a;
+    gsum = a.take(b * per_clip * 4);
+    rowt = a.take(b * K * 4);
+    score = a.take(b * K * 4);
+    return a.top;
   }
 };
 
-// Scores of the b * K path points x0 + alpha[k] (x - x0), as run_blob_scores runs its candidates: chunks of the plan's B
-// rows across clip boundaries, ivf_ig_stage -> forward -> blob_pick.  scores [b,K].
+// Scores of the b * K path points x0 + alpha[k] (x - x0), as run_blob_scores runs its candidates: per chunk
+// ivf_ig_stage -> forward -> blob_pick.  scores [b,K].
 static inline int run_ig_path_scores(const Backbone& v, const float* x, int b, const int* target, int base_kind,
                                      const float* base, float base_value, const float* alpha, int K, float* scores,
                                      hipStream_t s) {
-  const long long total = (long long)b * K;
-  for (long long first = 0; first < total; first += v.B) {
-    const int cnt = (int)std::min<long long>(v.B, total - first);
+  return for_each_chunk(v, (long long)b * K, [&](long long first, int cnt) -> int {
     IVF_PROPAGATE(ivf_ig_stage(x, base_kind, base, base_value, alpha, b, v.C, v.T, v.HW, K, first, cnt, v.in, v.layout, s));
     IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
-    IVF_PROPAGATE(blob_pick(v.probs, target, v.K, K, first, cnt, scores, s));
-  }
-  return IVF_OK;
+    return blob_pick(v.probs, target, v.K, K, first, cnt, scores, s);
+  });
 }
 
 // Integrated Gradients of b clips: per chunk of the plan's B rows stage -> forward -> backward -> accumulate, then
@@ -243,14 +243,12 @@ static int run_ig(const Backbone& v, const float* x, int b, const int* target, i
   float* score = path_scores ? path_scores : (float*)((char*)ws + c.score);
   IVF_CHECK_HIP(hipMemsetAsync(Gsum, 0, (size_t)b * per_clip * 4, s));
   IVF_PROPAGATE(ig_row_targets(target, b, K, rowt, s));
-  const long long total = (long long)b * K;
-  for (long long first = 0; first < total; first += v.B) {
-    const int cnt = (int)std::min<long long>(v.B, total - first);
+  IVF_PROPAGATE(for_each_chunk(v, (long long)b * K, [&](long long first, int cnt) -> int {
     IVF_PROPAGATE(ivf_ig_stage(x, base_kind, base, base_value, alpha, b, v.C, v.T, v.HW, K, first, cnt, v.in, v.layout, s));
     IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
     IVF_PROPAGATE(v.backward(v.plan, cnt, rowt + first, score + first, s));
-    IVF_PROPAGATE(ivf_ig_accumulate(v.din, v.layout, w, K, first, cnt, Gsum, b, v.C, v.T, v.HW, s));
-  }
+    return ivf_ig_accumulate(v.din, v.layout, w, K, first, cnt, Gsum, b, v.C, v.T, v.HW, s);
+  }));
   return ivf_ig_finish(x, base_kind, base, base_value, Gsum, b, v.C, v.T, v.HW, ig_map, frames, abs_frames, total_out, s);
 }
 

@@ -17,7 +17,6 @@
 namespace ivf {
 
 constexpr int ST_MAX_GRID = 32;   // gh, gw
-constexpr int ST_MAX_T = 64;      // the backward keeps a pixel's frames in registers (as MAX_T of mask_ops.hip)
 
 // ---------------------------------------------------------------- expand forward
 // One block per (b*T + t, tile of 32 rows); columns in chunks of 128.  Per chunk: A_W rows of the chunk to LDS, then
@@ -137,115 +136,6 @@ __global__ __launch_bounds__(256) void stmask_expand_bwd_kernel(const float* __r
   }
   __syncthreads();
   for (int i = tid; i < gh * gw; i += 256) dS[(size_t)bt * gh * gw + i] = ds_s[i];
-}
-
-// ---------------------------------------------------------------- per-pixel freeze forward
-// The recurrence of freeze_fwd_kernel (mask_ops.hip) with the mask value of the pixel: the same expression in the
-// same order, so a spatially constant M reproduces ivf_freeze_fwd bit for bit.  NCTHW: one thread per (b, c, pixel).
-__global__ void stfreeze_fwd_kernel(const float* __restrict__ x, const float* __restrict__ M, float* __restrict__ p,
-                                    int B, int C, int T, int HW) {
-  size_t total = (size_t)B * C * HW;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    int px = i % HW;
-    int c = (i / HW) % C;
-    int b = i / ((size_t)HW * C);
-    const float* xp = x + ((size_t)(b * C + c) * T) * HW + px;
-    const float* mp = M + (size_t)b * T * HW + px;
-    float* pp = p + ((size_t)(b * C + c) * T) * HW + px;
-    float prev = 0.f;
-    for (int u = 0; u < T; ++u) {
-      float xv = xp[(size_t)u * HW];
-      float v;
-      if (u == 0) {
-        v = xv;
-      } else {
-        float m = mp[(size_t)u * HW];
-        v = (1.f - m) * xv + m * prev;
-      }
-      prev = v;
-      pp[(size_t)u * HW] = v;
-    }
-  }
-}
-
-// channels-last rows of any width cpad >= C: one thread per (b, pixel) scans channel after channel and writes the pad
-// lanes as +0.0 itself
-__global__ void stfreeze_fwd_cl_kernel(const float* __restrict__ x, const float* __restrict__ M, float* __restrict__ p,
-                                       int B, int C, int T, int HW, int cpad) {
-  size_t total = (size_t)B * HW;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    int px = i % HW;
-    int b = i / HW;
-    const float* mp = M + (size_t)b * T * HW + px;
-    for (int c = 0; c < cpad; ++c) {
-      float prev = 0.f;
-      for (int u = 0; u < T; ++u) {
-        float v = 0.f;
-        if (c < C) {
-          float xv = x[((size_t)(b * C + c) * T + u) * HW + px];
-          if (u == 0) {
-            v = xv;
-          } else {
-            float m = mp[(size_t)u * HW];
-            v = (1.f - m) * xv + m * prev;
-          }
-          prev = v;
-        }
-        p[((size_t)(b * T + u) * HW + px) * cpad + c] = v;
-      }
-    }
-  }
-}
-
-// 16-byte channels-last pixels (C <= 4), one thread per (b, pixel), as freeze_fwd_cl4_kernel: with TT > 0 (T == TT)
-// all 16 frames of a piece -- the clip's and the mask's -- are requested before the scan goes over them.
-template <int TT>   // 0, or a multiple of 16
-__global__ __launch_bounds__(256) void stfreeze_fwd_cl4_kernel(const float* __restrict__ x, const float* __restrict__ M,
-                                                               float* __restrict__ p, int B, int C, int T, int HW) {
-  size_t total = (size_t)B * HW;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    int px = i % HW;
-    int b = i / HW;
-    const float* mp = M + (size_t)b * T * HW + px;
-    float prev[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (TT > 0) {
-#pragma unroll 1
-      for (int u0 = 0; u0 < TT; u0 += 16) {
-        float xv[4][16], m[16];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-          for (int j = 0; j < 16; ++j) {
-            xv[c][j] = 0.f;
-            if (c < C) xv[c][j] = x[((size_t)(b * C + c) * TT + u0 + j) * HW + px];
-          }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) m[j] = u0 + j ? mp[(size_t)(u0 + j) * HW] : 0.f;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-            if (c < C) {
-              v[c] = u0 + j ? (1.f - m[j]) * xv[c][j] + m[j] * prev[c] : xv[c][j];
-              prev[c] = v[c];
-            }
-          *reinterpret_cast<float4*>(p + ((size_t)(b * TT + u0 + j) * HW + px) * 4) = make_float4(v[0], v[1], v[2], v[3]);
-        }
-      }
-    } else {
-      for (int u = 0; u < T; ++u) {
-        float m = u ? mp[(size_t)u * HW] : 0.f;
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int c = 0; c < C; ++c) {
-          float xv = x[((size_t)(b * C + c) * T + u) * HW + px];
-          v[c] = u ? (1.f - m) * xv + m * prev[c] : xv;
-          prev[c] = v[c];
-        }
-        *reinterpret_cast<float4*>(p + ((size_t)(b * T + u) * HW + px) * 4) = make_float4(v[0], v[1], v[2], v[3]);
-      }
-    }
-  }
 }
 
 // ---------------------------------------------------------------- per-pixel freeze backward
@@ -432,7 +322,7 @@ __global__ __launch_bounds__(256) void stmask_step_kernel(float* __restrict__ ra
 //   rw[x]   = sum_{j in columns, ascending} A_W[x,j]
 //   M[y,x]  = sum_{i in rows, ascending} A_H[y,i] * rw[x]      on the blob's frames, 0 on the others,
 // every partial sum rounded as stmask_expand_fwd_kernel rounds it (this file is built without contraction: a multiply
-// and an add each).  The recurrence is stfreeze_fwd's expression with that M; on a frame with M = 0 it returns X[u].
+// and an add each).  The recurrence is ivf_stfreeze_fwd's expression with that M; on a frame with M = 0 it returns X[u].
 struct BoxAxes {
   int T, gh, gw, n_h, n_w, n;
 };
@@ -463,7 +353,7 @@ __device__ __forceinline__ float box_mask_at(const float* __restrict__ AH, const
   return m;
 }
 
-// 16-byte channels-last pixels (C <= 4): one thread per pixel of row blockIdx.y, as stfreeze_fwd_cl4_kernel.  With TT > 0
+// 16-byte channels-last pixels (C <= 4): one thread per pixel of row blockIdx.y, as freeze_fwd_cl4_kernel (mask_ops.hip).  With TT > 0
 // (T == TT) the 16 frames of a piece are requested before the scan goes over them.
 template <int TT>   // 0, or a multiple of 16
 __global__ __launch_bounds__(256) void box_stage_cl4_kernel(const float* __restrict__ x, const float* __restrict__ AH,
@@ -740,24 +630,8 @@ extern "C" int ivf_stfreeze_fwd(const float* x, const float* M, float* p, int B,
   IVF_CHECK_ARG(x && M && p, "stfreeze_fwd: null pointer");
   IVF_CHECK_ARG(B > 0 && C > 0 && T > 0 && HW > 0, "stfreeze_fwd: bad dims");
   IVF_CHECK_ARG(out_cpad == 0 || out_cpad >= C, "stfreeze_fwd: out_cpad (%d) < C (%d)", out_cpad, C);
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 block(256);
-  if (out_cpad == 0) {
-    hipLaunchKernelGGL(stfreeze_fwd_kernel, dim3(grid_for((size_t)B * C * HW, 256, 2048)), block, 0, s, x, M, p, B, C, T, HW);
-  } else if (out_cpad == 4) {
-    const dim3 grid(grid_for((size_t)B * HW, 256, 2048));
-    if (T == 16)
-      hipLaunchKernelGGL(stfreeze_fwd_cl4_kernel<16>, grid, block, 0, s, x, M, p, B, C, T, HW);
-    else if (T == 32)
-      hipLaunchKernelGGL(stfreeze_fwd_cl4_kernel<32>, grid, block, 0, s, x, M, p, B, C, T, HW);
-    else
-      hipLaunchKernelGGL(stfreeze_fwd_cl4_kernel<0>, grid, block, 0, s, x, M, p, B, C, T, HW);
-  } else {
-    hipLaunchKernelGGL(stfreeze_fwd_cl_kernel, dim3(grid_for((size_t)B * HW, 256, 2048)), block, 0, s, x, M, p, B, C, T, HW,
-                       out_cpad);
-  }
-  IVF_CHECK_LAUNCH();
-  return IVF_OK;
+  // the freeze scan of mask_ops.hip with the mask value of the pixel: a spatially constant M gives ivf_freeze_fwd's bits
+  return freeze_fwd(x, M, true, p, B, C, T, HW, 1, out_cpad, (hipStream_t)stream);
 }
 
 template <int TT>
@@ -780,15 +654,9 @@ static void stfreeze_bwd_launch(const float* x, const float* M, const float* g, 
 extern "C" int ivf_stfreeze_bwd(const float* x, const float* M, const float* g, float* dM, int B, int C, int T, int HW,
                                 int g_cpad, ivf_stream_t stream) {
   IVF_CHECK_ARG(x && M && g && dM, "stfreeze_bwd: null pointer");
-  IVF_CHECK_ARG(B > 0 && C > 0 && T > 0 && T <= ST_MAX_T && HW > 0, "stfreeze_bwd: bad dims (T <= %d)", ST_MAX_T);
+  IVF_CHECK_ARG(B > 0 && C > 0 && T > 0 && T <= MAX_T && HW > 0, "stfreeze_bwd: bad dims (T <= %d)", MAX_T);
   IVF_CHECK_ARG(g_cpad == 0 || g_cpad >= C, "stfreeze_bwd: g_cpad (%d) < C (%d)", g_cpad, C);
-  hipStream_t s = (hipStream_t)stream;
-  if (T <= 16)
-    stfreeze_bwd_launch<16>(x, M, g, dM, B, C, T, HW, g_cpad, s);
-  else if (T <= 32)
-    stfreeze_bwd_launch<32>(x, M, g, dM, B, C, T, HW, g_cpad, s);
-  else
-    stfreeze_bwd_launch<64>(x, M, g, dM, B, C, T, HW, g_cpad, s);
+  with_frames_upto(T, [&](auto TT) { stfreeze_bwd_launch<TT>(x, M, g, dM, B, C, T, HW, g_cpad, (hipStream_t)stream); });
   IVF_CHECK_LAUNCH();
   return IVF_OK;
 }
@@ -796,7 +664,7 @@ extern "C" int ivf_stfreeze_bwd(const float* x, const float* M, const float* g, 
 extern "C" int ivf_stmask_reg(const float* raw, int B, int T, int gh, int gw, float lam1, float lam2, float lam3,
                               float* sig, float* terms, float* dreg_dsig, ivf_stream_t stream) {
   IVF_CHECK_ARG(raw && sig && terms && dreg_dsig, "stmask_reg: null pointer");
-  IVF_CHECK_ARG(B > 0 && T > 0 && T <= ST_MAX_T, "stmask_reg: bad dims (T <= %d)", ST_MAX_T);
+  IVF_CHECK_ARG(B > 0 && T > 0 && T <= MAX_T, "stmask_reg: bad dims (T <= %d)", MAX_T);
   IVF_CHECK_ARG(st_grid_ok(gh, gw), "stmask_reg: grid %dx%d outside 1..%d", gh, gw, ST_MAX_GRID);
   hipLaunchKernelGGL(stmask_reg_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, raw, T, gh, gw, lam1, lam2, lam3, sig,
                      terms, dreg_dsig);
@@ -810,11 +678,10 @@ extern "C" int ivf_stmask_step(float* raw, const float* sig, const float* dscore
                                float beta2, float eps, ivf_stream_t stream) {
   IVF_CHECK_ARG(raw && sig && dscore_dsig && dreg_dsig && terms && score && exp_avg && exp_avg_sq,
                 "stmask_step: null pointer");
-  IVF_CHECK_ARG(B > 0 && T > 0 && T <= ST_MAX_T && step >= 1, "stmask_step: bad dims (T <= %d)", ST_MAX_T);
+  IVF_CHECK_ARG(B > 0 && T > 0 && T <= MAX_T && step >= 1, "stmask_step: bad dims (T <= %d)", MAX_T);
   IVF_CHECK_ARG(st_grid_ok(gh, gw), "stmask_step: grid %dx%d outside 1..%d", gh, gw, ST_MAX_GRID);
-  // adam_coeffs of mask_ops.hip
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  const float ss = (float)((double)lr / bc1), isb = (float)(1.0 / sqrt(bc2));
+  float ss, isb;
+  adam_coeffs(step, lr, beta1, beta2, &ss, &isb);
   hipLaunchKernelGGL(stmask_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, raw, sig, dscore_dsig, dreg_dsig,
                      terms, score, exp_avg, exp_avg_sq, traj_row, T * gh * gw, ss, isb, beta1, beta2, eps);
   IVF_CHECK_LAUNCH();
@@ -824,8 +691,8 @@ extern "C" int ivf_stmask_step(float* raw, const float* sig, const float* dscore
 // Caller-owned scratch of the spacetime search loop (search_driver.h, StScratch): M, dM [B,T,H,W]; sig, dreg, dsig
 // [B,T,gh,gw]; terms [B,3]; score [B]; every piece 256-byte aligned.  0 (message set) for arguments the loop refuses.
 extern "C" size_t ivf_stsearch_workspace_bytes(int B, int T, int H, int W, int gh, int gw) {
-  if (B <= 0 || T <= 0 || T > ST_MAX_T || H <= 0 || W <= 0 || !st_grid_ok(gh, gw)) {
-    set_error("stsearch_workspace_bytes: bad dims (T <= %d, grid 1..%d)", ST_MAX_T, ST_MAX_GRID);
+  if (B <= 0 || T <= 0 || T > MAX_T || H <= 0 || W <= 0 || !st_grid_ok(gh, gw)) {
+    set_error("stsearch_workspace_bytes: bad dims (T <= %d, grid 1..%d)", MAX_T, ST_MAX_GRID);
     return 0;
   }
   StScratch sc;
@@ -834,10 +701,10 @@ extern "C" size_t ivf_stsearch_workspace_bytes(int B, int T, int H, int W, int g
 
 // ---------------------------------------------------------------- one-box search: C-ABI
 extern "C" long long ivf_box_count(int T, int max_len, int gh, int gw, int mh, int mw) {
-  if (T < 1 || T > ST_MAX_T || max_len < 1 || max_len > T || !st_grid_ok(gh, gw) || mh < 1 || mh > gh || mw < 1 ||
+  if (T < 1 || T > MAX_T || max_len < 1 || max_len > T || !st_grid_ok(gh, gw) || mh < 1 || mh > gh || mw < 1 ||
       mw > gw) {
     set_error("box_count: need 1 <= max_len (%d) <= T (%d) <= %d, 1 <= mh (%d) <= gh (%d) <= %d, 1 <= mw (%d) <= gw (%d) <= %d",
-              max_len, T, ST_MAX_T, mh, gh, ST_MAX_GRID, mw, gw, ST_MAX_GRID);
+              max_len, T, MAX_T, mh, gh, ST_MAX_GRID, mw, gw, ST_MAX_GRID);
     return -1;
   }
   return (long long)ivf_blob_count(T, max_len) * ivf_blob_count(gh, mh) * ivf_blob_count(gw, mw);   // < 2^31 at the limits
@@ -861,12 +728,10 @@ extern "C" int ivf_box_stage(const float* x, int b, int C, int T, int H, int W, 
   const dim3 grid(cdiv(HW, 256), count), block(256);
   if (out_cpad == 0)
     hipLaunchKernelGGL(box_stage_ncthw_kernel, grid, block, 0, s, x, A_H, A_W, p, C, W, HW, ax, first);
-  else if (T == 16)
-    hipLaunchKernelGGL(box_stage_cl4_kernel<16>, grid, block, 0, s, x, A_H, A_W, p, C, W, HW, ax, first);
-  else if (T == 32)
-    hipLaunchKernelGGL(box_stage_cl4_kernel<32>, grid, block, 0, s, x, A_H, A_W, p, C, W, HW, ax, first);
   else
-    hipLaunchKernelGGL(box_stage_cl4_kernel<0>, grid, block, 0, s, x, A_H, A_W, p, C, W, HW, ax, first);
+    with_frames_exact(T, [&](auto TT) {
+      hipLaunchKernelGGL(box_stage_cl4_kernel<TT>, grid, block, 0, s, x, A_H, A_W, p, C, W, HW, ax, first);
+    });
   IVF_CHECK_LAUNCH();
   return IVF_OK;
 }

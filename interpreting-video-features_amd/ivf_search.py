@@ -209,6 +209,35 @@ def box_masks(best, T, grid):
     return (t[:, :, None, None] * h[:, None, :, None] * w[:, None, None, :]).contiguous()
 
 
+def frame_means(S):
+    """Spatial mean per frame [b,T] of S [b,T,gh,gw]: ivf_stmask_expand_fwd onto a single pixel (H = W = 1) with the
+    uniform rows 1/gh, 1/gw as its two matrices -- the same fixed-order sums as everywhere else, no new kernel (see
+    ivf_hip.h)."""
+    b, T, gh, gw = S.shape
+    dev = S.device
+    mean = torch.empty(b, T, device=dev)
+    ah, aw = torch.full((1, gh), 1.0 / gh, device=dev), torch.full((1, gw), 1.0 / gw, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().ivf_stmask_expand_fwd(L.ptr(S), L.ptr(ah), L.ptr(aw), L.ptr(mean), b, T, gh, gw, 1, 1, L.stream()))
+    return mean
+
+
+def score_at(scores, k):
+    """scores[i, k[i]] of a score grid [b,n]; NaN where k[i] < 0 (no candidate picked)."""
+    b = scores.shape[0]
+    idx = torch.arange(b, device=scores.device)
+    return torch.where(k >= 0, scores[idx, k.clamp(min=0)], torch.full((b,), float("nan"), device=scores.device))
+
+
+def time_mask_outputs(eng, x, target, mask, out):
+    """From a time_mask [b,T]: the score of the reversed clip (smth:234-235), the frame ranking and the snapped mask
+    (mask.py:5-10)."""
+    idx = torch.arange(x.shape[0], device=x.device)
+    out["reverse_score"] = eng.perturbed_forward(x, mask, "reverse")[idx, target.long()]
+    out["ranking"] = frame_ranking(mask)
+    out["snapped"] = mask > 0.5
+
+
 class MaskSearch:
     def __init__(self, engine, lam1=0.01, lam2=0.02, n_iter=300, mask_type="freeze", threshold=0.9,
                  lr=0.2, grad_cam_type="guessed", do_gradcam=True, run_temp_mask=True,
@@ -278,10 +307,7 @@ class MaskSearch:
                 L.check(L.lib().ivf_sigmoid(L.ptr(raw), L.ptr(mask), raw.numel(), L.stream()))
             out["time_mask"] = mask
             out["freeze_score"] = traj[-1, :, 3] if self.n_iter > 0 else torch.full((b,), float("nan"), device=dev)
-            rev = eng.perturbed_forward(x, mask, "reverse")                  # smth:234-235
-            out["reverse_score"] = rev[idx, target.long()]
-            out["ranking"] = frame_ranking(mask)
-            out["snapped"] = mask > 0.5                                      # mask.py:5-10
+            time_mask_outputs(eng, x, target, mask, out)
             if want_traj:
                 out["traj"] = traj
         if self.do_gradcam:
@@ -310,11 +336,8 @@ class MaskSearch:
         mask = blob_masks(sel["best"], T)
         k = blob_index(sel["best"], T)
         out["time_mask"] = mask
-        out["freeze_score"] = torch.where(k >= 0, scores[idx, k.clamp(min=0)],
-                                          torch.full((b,), float("nan"), device=dev))     # the loop-type score
-        out["reverse_score"] = eng.perturbed_forward(x, mask, "reverse")[idx, tl]            # smth:234-235
-        out["ranking"] = frame_ranking(mask)
-        out["snapped"] = mask > 0.5
+        out["freeze_score"] = score_at(scores, k)                                             # the loop-type score
+        time_mask_outputs(eng, x, target, mask, out)
         out["blob"] = sel["best"]
         out["blob_objective"] = sel["objective"]
         out["blob_minimal"] = sel["minimal"]
@@ -341,19 +364,13 @@ class MaskSearch:
         traj, _ = eng.st_search(x, target, raw, self.lam1, self.lam2, self.n_iter, (gh, gw), self.mask_sigma,
                                 lam3=self.lam3, lr=self.lr, want_traj=True)
         S = torch.empty_like(raw)
-        mean = torch.empty(b, T, device=dev)
-        ah, aw = torch.full((1, gh), 1.0 / gh, device=dev), torch.full((1, gw), 1.0 / gw, device=dev)
         with torch.cuda.device(dev):
             L.check(L.lib().ivf_sigmoid(L.ptr(raw), L.ptr(S), raw.numel(), L.stream()))
-            # the spatial mean per frame = the expand onto a single pixel (H = W = 1) with the uniform rows 1/gh, 1/gw
-            # as its two matrices: the same fixed-order sums as everywhere else, no new kernel (see ivf_hip.h)
-            L.check(L.lib().ivf_stmask_expand_fwd(L.ptr(S), L.ptr(ah), L.ptr(aw), L.ptr(mean), b, T, gh, gw, 1, 1, L.stream()))
+        mean = frame_means(S)
         out["st_mask"] = S
         out["time_mask"] = mean
         out["freeze_score"] = traj[-1, :, 4] if self.n_iter > 0 else torch.full((b,), float("nan"), device=dev)
-        out["reverse_score"] = eng.perturbed_forward(x, mean, "reverse")[idx, target.long()]
-        out["ranking"] = frame_ranking(mean)
-        out["snapped"] = mean > 0.5
+        time_mask_outputs(eng, x, target, mean, out)
         if want_traj:
             out["traj"] = traj
 
@@ -366,24 +383,18 @@ class MaskSearch:
         dev = x.device
         idx = torch.arange(b, device=dev)
         tl = target.long()
-        grid = gh, gw = self.st_grid(x)
+        grid = self.st_grid(x)
         orig = probs[idx, tl]
         full = eng.perturbed_forward(x, torch.ones(b, T, device=dev), "freeze")[idx, tl]     # mask.py:123-128
         scores = eng.box_scores(x, target, grid, self.mask_sigma, self.max_mask_length, self.max_box)
         sel = box_select(scores, orig, full, T, grid, self.max_mask_length, self.max_box, self.lam1, self.lam2, self.lam3,
                          self.threshold)
         S = box_masks(sel["best"], T, grid)
-        mean = torch.empty(b, T, device=dev)
-        ah, aw = torch.full((1, gh), 1.0 / gh, device=dev), torch.full((1, gw), 1.0 / gw, device=dev)
-        with torch.cuda.device(dev):
-            L.check(L.lib().ivf_stmask_expand_fwd(L.ptr(S), L.ptr(ah), L.ptr(aw), L.ptr(mean), b, T, gh, gw, 1, 1, L.stream()))
-        k = sel["index"]
+        mean = frame_means(S)
         out["st_mask"] = S
         out["time_mask"] = mean
-        out["freeze_score"] = torch.where(k >= 0, scores[idx, k.clamp(min=0)], torch.full((b,), float("nan"), device=dev))
-        out["reverse_score"] = eng.perturbed_forward(x, mean, "reverse")[idx, tl]
-        out["ranking"] = frame_ranking(mean)
-        out["snapped"] = mean > 0.5
+        out["freeze_score"] = score_at(scores, sel["index"])
+        time_mask_outputs(eng, x, target, mean, out)
         out["box"] = sel["best"]
         out["box_objective"] = sel["objective"]
         out["box_minimal"] = sel["minimal"]

@@ -46,9 +46,10 @@ def _gen(*key):
 
 
 # ------------------------------------------------------------------------------------------------ freeze: case table
-# (B, C, T, HW).  Kernels and template instantiations each case launches (fwd: NCTHW / out_cpad 4 / out_cpad 8;
-# bwd: g NCTHW / g_cpad 4 / g_cpad 8, each with and without dX; every bwd ends in freeze_bwd_reduce):
-#   F1  freeze_fwd, freeze_fwd_cl4, zero_kernel; freeze_bwd<16> with C*HW = 37635: three trips of 16384, the last
+# (B, C, T, HW).  Kernels and template instantiations each case launches (fwd, the frame-mask kind of the freeze-scan
+# family: NCTHW freeze_fwd_ncthw / out_cpad 4 freeze_fwd_cl4<TT> / out_cpad 8 freeze_fwd_cl, which writes its own pad
+# lanes; bwd: g NCTHW / g_cpad 4 / g_cpad 8, each with and without dX; every bwd ends in freeze_bwd_reduce):
+#   F1  freeze_fwd_ncthw, freeze_fwd_cl4<16>, freeze_fwd_cl; freeze_bwd<16> with C*HW = 37635: three trips of 16384, the last
 #       ragged (4867) and not block-aligned; freeze_bwd_cl4<16> one trip
 #   F2  freeze_bwd_cl4<16> second trip (HW = 20003 > 16384, ragged); freeze_bwd<16> with four trips (60009)
 #   F3  C = 1, 65 clips (more clips than one wave of blocks), T = 9 ragged inside <16>, 63 of 64 blocks empty
@@ -57,10 +58,10 @@ def _gen(*key):
 #   F6  freeze_bwd<32> and freeze_bwd_cl4<32> with 15 guarded frames
 #   F7  freeze_bwd<64> full
 #   F8  T = 1: p == x, dmask == 0.0, dx == g
-#   F9  forward grid cap (2048 blocks of 256): freeze_fwd 1 655 808 threads (four trips), freeze_fwd_cl4 551 936 (two
-#       trips), zero_kernel 8.8 M (17 trips); 13 MB of input.  Its out_cpad 8 output is 35 MB (out_cpad 8 runs on every
+#   F9  forward grid cap (2048 blocks of 256): freeze_fwd_ncthw 1 655 808 threads (four trips), freeze_fwd_cl4<0> and
+#       freeze_fwd_cl 551 936 each (two trips); 13 MB of input.  Its out_cpad 8 output is 35 MB (out_cpad 8 runs on every
 #       case).  Backward: ten trips of the generic kernel, four of the channels-last one (also an exact case).
-#   F10 C > 4: freeze_fwd with out_cpad 8 after zero_kernel (out_cpad 4 is refused), backward with g_cpad 8
+#   F10 C > 4: freeze_fwd_cl with out_cpad 8 (out_cpad 4 is refused), backward with g_cpad 8
 # The generic backward with dX and a channels-last gradient together runs in every case.
 FREEZE_CASES = {
     'F1': (2, 3, 16, 12545),
@@ -94,7 +95,8 @@ def out_layouts(C):
 
 
 def bwd_kernel(C, T, g_cpad, dx):
-    """which backward kernel ivf_freeze_bwd launches: ('cl4' | 'generic', template T)"""
+    """which backward kernel ivf_freeze_bwd launches: ('cl4' = freeze_bwd_cl4_kernel | 'generic' = freeze_bwd_kernel,
+    template T as with_frames_upto of csrc/ivf_common.h picks it)"""
     TT = 16 if T <= 16 else (32 if T <= 32 else 64)
     return ('cl4' if (g_cpad == 4 and C <= 4 and not dx and T <= 32) else 'generic'), TT
 
