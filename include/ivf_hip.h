@@ -243,6 +243,33 @@ int ivf_box_select(const float* scores, const float* orig, const float* full, in
 int ivf_box_drop(const float* scores, const float* orig, int b, int T, int gh, int gw, int max_len, int mh, int mw,
                  float* drop, ivf_stream_t stream);
 
+/* ------------------------------------------------------------------ RISE random-mask saliency (csrc/rise_ops.hip)
+ * An EXTENSION with no counterpart in the reference (Petsiuk et al. 2018): n random coarse masks, one
+ * forward each, a cell's importance = the mean score drop over the masks that froze it.  A mask lives on a grid
+ * (gt, gh, gw), 1 <= gt <= T <= 64, 1 <= gh, gw <= 32; frame u belongs to temporal cell kt = (u gt) / T, cell
+ * c = (kt gh + i) gw + j.  Mask k is the same for every clip; it freezes cell c iff
+ *   fmix32( fmix32(seed + 0x9E3779B9 (k + 1)) ^ (0x85EBCA77 (c + 1)) ) < thresh          (uint32, wrapping;
+ *   fmix32(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16)
+ * with thresh = floor(p 2^32) computed by the caller, 0 refused.  No entry stores the masks: the bits are regenerated.
+ *
+ * Explicit bits of masks [first_k, first_k+count) as 0.0 / 1.0 into S [count,gt,gh,gw]. */
+int ivf_rise_masks(unsigned seed, unsigned thresh, int first_k, int count, int gt, int gh, int gw, float* S,
+                   ivf_stream_t stream);
+/* Rows [first, first+count) of the flattened (clip, mask) list of b clips x [b,C,T,H,W] into p; row j is clip
+ * (first+j)/n under mask (first+j)%n; count <= 65535.  out_cpad as the box staging entry: 0 NCTHW [count,C,T,HW], 4 16-byte
+ * channels-last pixels [count,T,HW,4] (C <= 4, pad lanes +0.0, p 16-byte aligned).  A_H [H,gh], A_W [W,gw] on the
+ * device, finite and non-negative.  The rows equal (==) what ivf_stmask_expand_fwd followed by ivf_stfreeze_fwd write
+ * for the row's explicit per-frame S (S[u] = S_k[kt(u)]); neither S nor M is ever in memory. */
+int ivf_rise_stage(const float* x, int b, int C, int T, int H, int W, const float* A_H, const float* A_W, int gt, int gh,
+                   int gw, int n, unsigned seed, unsigned thresh, long long first, int count, float* p, int out_cpad,
+                   ivf_stream_t stream);
+/* The estimator from scores [b,n] and orig [b], d_k = orig - s_k, k ascending in plain fp32 adds, one thread per
+ * (clip, cell), no atomics: cells [b,gt,gh,gw] = sum of d_k over the masks that froze the cell / count, count (int)
+ * their number; a NaN score is neither summed nor counted; cells is NaN where count == 0.  mean_drop [b] = the mean of
+ * d_k over the clip's non-NaN scores. */
+int ivf_rise_reduce(const float* scores, const float* orig, int b, int n, unsigned seed, unsigned thresh, int gt, int gh,
+                    int gw, float* cells, int* count, float* mean_drop, ivf_stream_t stream);
+
 /* Clip ingest: the arithmetic of ImLoader.__getitem__ /
  * KTHImLoader.__getitem__ after the JPEG decode (data_loader_jpg.py:29-37,
  * data_loader_kth.py:25-44): uint8 frames [B][T][H][W][C] -> float32 (exact), permuted to
@@ -538,6 +565,12 @@ int ivf_i3d_blob_scores(ivf_i3d_t* net, const float* x, int b, const int* target
  * exceed B.  One stream, no host synchronisation, no allocation. */
 int ivf_i3d_box_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W, int gh,
                       int gw, int max_len, int mh, int mw, float* scores, ivf_stream_t stream);
+/* Scores of the n RISE masks of b clips (extension, see ivf_rise_*): scores [b,n] = probs[target[clip]] of the clip
+ * frozen per pixel by mask k, in chunks of the plan's B rows (ivf_rise_stage -> forward -> pick); b may exceed B.  One
+ * stream, no host synchronisation, no allocation, no scratch beyond scores. */
+int ivf_i3d_rise_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
+                        int gt, int gh, int gw, int n, unsigned seed, unsigned thresh, float* scores,
+                        ivf_stream_t stream);
 
 /* Integrated Gradients of b clips through this plan (extension, see ivf_ig_*): the b*K path points run in chunks of the
  * plan's B rows across clip boundaries (ivf_ig_stage -> forward -> backward -> ivf_ig_accumulate), then ivf_ig_finish;
@@ -640,6 +673,10 @@ int ivf_clstm_blob_scores(ivf_clstm_t* net, const float* x, int b, const int* ta
  * exceed B.  One stream, no host synchronisation, no allocation. */
 int ivf_clstm_box_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W, int gh,
                       int gw, int max_len, int mh, int mw, float* scores, ivf_stream_t stream);
+/* ivf_i3d_rise_scores with the ConvLSTM backbone (rows staged NCTHW). */
+int ivf_clstm_rise_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
+                          int gt, int gh, int gw, int n, unsigned seed, unsigned thresh, float* scores,
+                          ivf_stream_t stream);
 
 /* Integrated Gradients of b clips through this plan (extension, see ivf_ig_*): the b*K path points run in chunks of the
  * plan's B rows across clip boundaries (ivf_ig_stage -> forward -> backward -> ivf_ig_accumulate), then ivf_ig_finish;

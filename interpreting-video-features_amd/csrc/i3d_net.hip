@@ -894,6 +894,17 @@ extern "C" int ivf_i3d_box_scores(ivf_i3d_t* net, const float* x, int b, const i
                         (hipStream_t)stream);
 }
 
+// RISE random-mask saliency (rise_ops.hip): run_rise_scores, rows staged straight into the input buffer.
+extern "C" int ivf_i3d_rise_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H,
+                                   const float* A_W, int gt, int gh, int gw, int n, unsigned seed, unsigned thresh,
+                                   float* scores, ivf_stream_t stream) {
+  IVF_PROPAGATE(check_ready(net, 1));
+  IVF_CHECK_ARG(x && target && A_H && A_W && scores, "i3d_rise_scores: null pointer");
+  IVF_CHECK_ARG(b > 0 && n > 0, "i3d_rise_scores: bad batch %d or mask count %d", b, n);
+  return run_rise_scores(backbone(net), x, b, target, A_H, A_W, gt, gh, gw, net->cfg.H, net->cfg.W, n, seed, thresh,
+                         scores, (hipStream_t)stream);
+}
+
 // Integrated Gradients (ig_ops.hip): run_ig / run_ig_path_scores on this plan; scratch from the caller.
 extern "C" int ivf_i3d_ig(ivf_i3d_t* net, const float* x, int b, const int* target, int base_kind, const float* base,
                           float base_value, const float* alpha, const float* w, int K, float* ig_map, float* frames,

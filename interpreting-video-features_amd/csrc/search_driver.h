@@ -201,6 +201,19 @@ static inline int run_box_scores(const Backbone& v, const float* x, int b, const
   });
 }
 
+// RISE random-mask saliency (rise_ops.hip; an extension): run_box_scores with the random-mask staging -- per
+// chunk ivf_rise_stage -> forward -> blob_pick on the b * n (clip, mask) rows, one stream, no host synchronisation, no
+// allocation, no scratch beyond `scores`.
+static inline int run_rise_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,
+                                  const float* A_W, int gt, int gh, int gw, int H, int W, int n, unsigned seed,
+                                  unsigned thresh, float* scores, hipStream_t s) {
+  return for_each_chunk(v, (long long)b * n, [&](long long first, int cnt) -> int {
+    IVF_PROPAGATE(ivf_rise_stage(x, b, v.C, v.T, H, W, A_H, A_W, gt, gh, gw, n, seed, thresh, first, cnt, v.in, v.layout, s));
+    IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
+    return blob_pick(v.probs, target, v.K, n, first, cnt, scores, s);
+  });
+}
+
 // ---------------------------------------------------------------- Integrated Gradients (ig_ops.hip)
 // An extension without a counterpart in the reference.  Its scratch belongs to the CALLER (ivf_ig_workspace_bytes), so
 // no plan's workspace size or carve order moves.

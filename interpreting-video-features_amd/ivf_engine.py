@@ -5,6 +5,7 @@ the allocator, nothing more -- and exposes the plan's entry points with torch
 tensors in/out.  Everything that computes is in csrc/*.hip.
 """
 import ctypes
+import math
 import os
 from ctypes import byref, c_char, c_int, c_void_p
 
@@ -29,6 +30,26 @@ def _mode_id(mode):
     if mode == "reverse":
         return 1
     raise UnboundLocalError("local variable 'perturbed_input' referenced before assignment")
+
+
+def default_st_grid(H, W):
+    """spatial mask grid where none is given: one cell per 32 input pixels (7x7 at 224^2, 4x5 at 120x160)"""
+    return max(1, round(H / 32)), max(1, round(W / 32))
+
+
+def rise_thresh(p):
+    """The integer threshold of the RISE mask hash, computed here and nowhere else: a cell is frozen iff
+    its 32-bit hash < floor(p 2^32), 0 < p < 1 (a p below 2^-32 would freeze nothing and is refused as well)."""
+    try:
+        p = float(p)
+    except (TypeError, ValueError):
+        raise L.IvfError(f"p must be a number in (0, 1), got {p!r}")
+    if not 0.0 < p < 1.0:
+        raise L.IvfError(f"p must be in (0, 1), got {p}")
+    thresh = int(math.floor(p * 4294967296.0))
+    if thresh < 1:
+        raise L.IvfError(f"p = {p} is below 2^-32: no cell would ever be frozen")
+    return thresh
 
 
 def _arena(nbytes, device):
@@ -387,6 +408,94 @@ class _Engine:
         out["ig_gap"] = out["ig_total"] - (out["score_x"] - out["score_base"])
         return out
 
+    # -------------------------------------------------------------- RISE random-mask saliency (extension)
+    def _rise_args(self, n_masks, p, grid, sigma, seed):
+        """(gt, gh, gw, n, seed, thresh, A_H, A_W) of a RISE call, checked; grid None -> (min(T, 8),) + the spatial
+        grid of the spacetime search (one cell per 32 input pixels)."""
+        if not self._has_st:
+            raise L.IvfError("RISE is built for the I3D and CLSTM plans only")
+        C, T, H, W = self.clip_shape
+        if grid is None:
+            grid = (min(T, 8),) + default_st_grid(H, W)
+        try:
+            gt, gh, gw = (int(v) for v in grid)
+        except (TypeError, ValueError):
+            raise L.IvfError(f"grid must be (gt, gh, gw), got {grid!r}")
+        if not (1 <= gt <= T <= 64 and 1 <= gh <= 32 and 1 <= gw <= 32):
+            raise L.IvfError(f"grid {(gt, gh, gw)}: need 1 <= gt <= T = {T} <= 64 and 1 <= gh, gw <= 32")
+        n, seed = int(n_masks), int(seed)
+        if n < 1:
+            raise L.IvfError(f"n_masks must be >= 1, got {n_masks}")
+        if not 0 <= seed < 2 ** 32:
+            raise L.IvfError(f"seed must be in [0, 2^32), got {seed}")
+        thresh = rise_thresh(p)
+        _, _, _, AH, AW = self._st_axes((gh, gw), sigma)
+        return gt, gh, gw, n, seed, thresh, AH, AW
+
+    def rise_masks(self, n_masks=1024, p=0.5, grid=None, seed=0, first=0):
+        """The sampled masks themselves (ivf_rise_masks): S [n_masks,gt,gh,gw] in {0, 1} of masks first ..
+        first + n_masks - 1, 1 = cell frozen.  The same for every clip."""
+        gt, gh, gw, n, seed, thresh, _, _ = self._rise_args(n_masks, p, grid, None, seed)
+        S = torch.empty(n, gt, gh, gw, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().ivf_rise_masks(seed, thresh, int(first), n, gt, gh, gw, L.ptr(S), L.stream()))
+        return S
+
+    def rise_scores(self, x, target, n_masks=1024, p=0.5, grid=None, sigma=None, seed=0):
+        """Scores [b, n_masks] of target[clip] with the clip frozen per pixel by each random mask (expanded as st_expand
+        expands it): ivf_*_rise_scores, forward only, chunks of the plan's max_batch rows; b may exceed max_batch."""
+        gt, gh, gw, n, seed, thresh, AH, AW = self._rise_args(n_masks, p, grid, sigma, seed)
+        x = self._clip(x, any_batch=True)
+        b = x.shape[0]
+        tgt = self._targets(target, b)
+        scores = torch.empty(b, n, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(self._fn("rise_scores")(self._h, L.ptr(x), b, L.ptr(tgt), L.ptr(AH), L.ptr(AW), gt, gh, gw, n, seed,
+                                            thresh, L.ptr(scores), L.stream()))
+        return scores
+
+    def rise_reduce(self, scores, orig, p=0.5, grid=None, seed=0):
+        """ivf_rise_reduce on scores [b,n] and orig [b]: (cells [b,gt,gh,gw], count int32, mean_drop [b])."""
+        s = L.f32c(scores)
+        L.require_gpu(s)
+        b, n = s.shape
+        gt, gh, gw, n, seed, thresh, _, _ = self._rise_args(n, p, grid, None, seed)
+        orig = L.f32c(orig.reshape(b))
+        cells = torch.empty(b, gt, gh, gw, device=s.device)
+        count = torch.empty(b, gt, gh, gw, dtype=torch.int32, device=s.device)
+        mean_drop = torch.empty(b, device=s.device)
+        with torch.cuda.device(s.device):
+            L.check(L.lib().ivf_rise_reduce(L.ptr(s), L.ptr(orig), b, n, seed, thresh, gt, gh, gw, L.ptr(cells),
+                                            L.ptr(count), L.ptr(mean_drop), L.stream()))
+        return cells, count, mean_drop
+
+    def rise(self, x, target, n_masks=1024, p=0.5, grid=None, sigma=None, seed=0):
+        """RISE (Petsiuk et al. 2018) of target[clip] on b clips, b may exceed max_batch: n_masks random masks on
+        grid = (gt, gh, gw), each cell frozen with probability p, one forward per mask, a cell's importance = the mean
+        of score_x - score over the masks that froze it.  Returns a dict of device tensors: rise_scores [b,n],
+        rise_cells [b,gt,gh,gw] (NaN where no mask froze the cell), rise_count (int32), rise_mean_drop [b], score_x [b]
+        (the plan's ordinary forward), rise_map [b,T,H,W] (the cells repeated over the frames of their temporal cell
+        and expanded with st_expand) and rise_frames [b,T] (its grid's spatial mean per frame)."""
+        gt, gh, gw, n, seed, thresh, AH, AW = self._rise_args(n_masks, p, grid, sigma, seed)
+        x = self._clip(x, any_batch=True)
+        b = x.shape[0]
+        C, T, H, W = self.clip_shape
+        tgt = self._targets(target, b)
+        idx = tgt.long().view(-1, 1)
+        score_x = torch.cat([self.forward(x[i:i + self.max_batch]).gather(1, idx[i:i + self.max_batch])
+                             for i in range(0, b, self.max_batch)])[:, 0].contiguous()
+        scores = self.rise_scores(x, tgt, n, p, (gt, gh, gw), sigma, seed)
+        cells, count, mean_drop = self.rise_reduce(scores, score_x, p, (gt, gh, gw), seed)
+        kt = (torch.arange(T, device=self.device) * gt) // T
+        S = cells[:, kt].contiguous()                                   # [b,T,gh,gw]
+        frames = torch.empty(b, T, device=self.device)
+        ah, aw = torch.full((1, gh), 1.0 / gh, device=self.device), torch.full((1, gw), 1.0 / gw, device=self.device)
+        with torch.cuda.device(self.device):                            # ivf_search.frame_means' uniform-row trick
+            L.check(L.lib().ivf_stmask_expand_fwd(L.ptr(S), L.ptr(ah), L.ptr(aw), L.ptr(frames), b, T, gh, gw, 1, 1,
+                                                  L.stream()))
+        return dict(rise_scores=scores, rise_cells=cells, rise_count=count, rise_mean_drop=mean_drop, score_x=score_x,
+                    rise_map=self.st_expand(S, (gh, gw), sigma), rise_frames=frames)
+
     def argmax(self, probs):
         b = probs.shape[0]
         t = torch.empty(b, dtype=torch.int32, device=self.device)
@@ -647,8 +756,8 @@ class TFCLSTMEngine(_Engine):
     (video_features_tf/models/clstm.py:87-126) and its temporal-mask search / per-frame Grad-CAM
     (mask/find_mask_kth.py:300-452, mask/gradcam.py:28-111) on libivf_hip's generic direct-convolution kernels
     (csrc/tf_clstm.hip).  Clips are NCTHW like everywhere else; `from_tf_layout` converts [B,T,H,W,C].
-    The plan perturbs by freezing only and has no one-blob entry (the inherited `blob_scores` finds no symbol); `ig`
-    and `ig_path_scores` refuse with IvfError."""
+    The plan perturbs by freezing only and has no one-blob entry (the inherited `blob_scores` finds no symbol); `ig`,
+    `ig_path_scores` and the `rise*` entries refuse with IvfError."""
     _prefix = "tfclstm"
     _has_mode = False
     _has_st = False

@@ -47,8 +47,16 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                     verbose=True, doGradCam=False, runTempMask=True, flavour="smth", sub_dir="run0",
                     results_path="results/", gradcam_size=None, write_files=True, device=None, visualise=True,
                     mask_mode="central", max_mask_length=None, blob_batch=32, mask_grid=None, mask_sigma=None, lam3=None,
-                    max_box=None, do_intgrad=False, ig_steps=32, ig_baseline="frozen"):
-    """do_intgrad (the drivers' doIntGrad, an extension: DESIGN 13) also runs Integrated Gradients of the target's score
+                    max_box=None, do_intgrad=False, ig_steps=32, ig_baseline="frozen", do_rise=False, rise_masks=1024,
+                    rise_p=0.5, rise_grid=None, rise_sigma=None, rise_seed=0):
+    """do_rise (the drivers' doRise, an extension: DESIGN 14) also runs RISE random-mask saliency of the target's score
+    (rise_masks masks on rise_grid (gt, gh, gw), each cell frozen with probability rise_p, blurred by rise_sigma input
+    pixels, drawn from rise_seed; forward passes only) and writes a further list of records -- true_class, pred_class,
+    video_id, RiseHeatMap [T,H,W], RiseCells [gt,gh,gw], RiseCount, RiseFrames [T], rise_mean_drop, n_masks, p, seed --
+    to a pickle named like the Grad-CAM one with Rise in place of GradCam; with the strips on, a further set of
+    heat-map strips (folder `rise` beside `combined`) blends max(rise_map, 0) normalised per frame; its plan holds at
+    least blob_batch clips so that the masks of a loader batch fill it.  Off, nothing changes.
+    do_intgrad (the drivers' doIntGrad, an extension: DESIGN 13) also runs Integrated Gradients of the target's score
     (ig_steps midpoint nodes from ig_baseline 'frozen' or 'constant') and writes a third list of records -- true_class,
     pred_class, video_id, IGHeatMap [T,H,W], IGFrames [T], ig_total, ig_gap, score_base -- to a third pickle named like
     the Grad-CAM one with IntGrad in place of GradCam; with the strips on, a second set of heat-map strips (folder
@@ -68,7 +76,7 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
     net = _unwrap(model)
     net.eval()                                                      # smth:145
     flt = _class_filter(classOI)
-    masks, time_results, cam_results, ig_results = [], [], [], []
+    masks, time_results, cam_results, ig_results, rise_results = [], [], [], [], []
     if write_files and not os.path.exists(results_path):
         os.makedirs(results_path)
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -86,16 +94,18 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
         if not keep:
             continue
         xs = x[keep].contiguous()
-        eng = net._engine_for(xs, min_batch=blob_batch) if mask_mode in ("combi", "stcombi") else net._engine_for(xs)
+        eng = net._engine_for(xs, min_batch=blob_batch) if mask_mode in ("combi", "stcombi") or do_rise \
+            else net._engine_for(xs)
         search = ivf_search.MaskSearch(eng, lam1, lam2, N, temporalMaskType, threshold=0.9, lr=0.2,
                                        grad_cam_type=hyper_params.get("gradCamType", "guessed"),
                                        do_gradcam=doGradCam, run_temp_mask=runTempMask,
                                        normalize_per_frame=True, gradcam_size=gradcam_size, mask_mode=mask_mode,
                                        max_mask_length=max_mask_length, mask_grid=mask_grid, mask_sigma=mask_sigma,
                                        lam3=lam3, max_box=max_box, do_intgrad=do_intgrad, ig_steps=ig_steps,
-                                       ig_baseline=ig_baseline)
+                                       ig_baseline=ig_baseline, do_rise=do_rise, rise_masks=rise_masks, rise_p=rise_p,
+                                       rise_grid=rise_grid, rise_sigma=rise_sigma, rise_seed=rise_seed)
         res = search.run(xs, labels[keep])
-        host = {k: v.detach().cpu() for k, v in res.items() if k not in ("gradcam", "box_scores", "ig_map")}
+        host = {k: v.detach().cpu() for k, v in res.items() if k not in ("gradcam", "box_scores", "ig_map", "rise_map")}
         spacetime = runTempMask and mask_mode in ("spacetime", "stcombi")
         st_maps = eng.st_expand(res["st_mask"], search.st_grid(xs), mask_sigma) if spacetime and write_files and visualise \
             else None
@@ -111,6 +121,14 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                 pos = res["ig_map"].clamp_min(0.0)
                 top = pos.amax(dim=(2, 3), keepdim=True)
                 ig_heat = torch.where(top > 0, pos / torch.where(top > 0, top, torch.ones_like(top)), torch.zeros_like(pos))
+        rise_heat = None
+        if do_rise:
+            host["rise_map"] = res["rise_map"].detach().cpu()
+            if runTempMask and write_files and visualise:
+                # as ig_heat: max(rise_map, 0) scaled to [0,1] per frame; a frame without a positive drop stays all zero
+                pos = res["rise_map"].clamp_min(0.0)
+                top = pos.amax(dim=(2, 3), keepdim=True)
+                rise_heat = torch.where(top > 0, pos / torch.where(top > 0, top, torch.ones_like(top)), torch.zeros_like(pos))
         for j, bi in enumerate(keep):
             true_class = int(labels[bi])
             pred = int(host["pred_class"][j])
@@ -156,6 +174,15 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                    'IGFrames': host["ig_frames"][j].numpy().astype(np.float32),
                                    'ig_total': float(host["ig_total"][j]), 'ig_gap': float(host["ig_gap"][j]),
                                    'score_base': float(host["ig_score_base"][j])})
+            if do_rise:
+                rise_results.append({'true_class': true_class, 'pred_class': pred,
+                                     'video_id': int(vid) if flavour == "smth" else vid,
+                                     'RiseHeatMap': host["rise_map"][j].numpy().astype(np.float32),
+                                     'RiseCells': host["rise_cells"][j].numpy().astype(np.float32),
+                                     'RiseCount': host["rise_count"][j].numpy(),
+                                     'RiseFrames': host["rise_frames"][j].numpy().astype(np.float32),
+                                     'rise_mean_drop': float(host["rise_mean_drop"][j]),
+                                     'n_masks': int(rise_masks), 'p': float(rise_p), 'seed': int(rise_seed)})
             if runTempMask and write_files and visualise:
                 # smth:296-303 / KTH:354-367: heat-map strips with the mask dot row for both perturbation
                 # types (the dot row snaps a host copy: `tmask` keeps its sigmoid values, as the reference's
@@ -168,6 +195,10 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                 if ig_heat is not None:
                     for kind in ("freeze", "reverse"):
                         viz.create_image_arrays(xs, ig_heat[j], tmask, j, kind, os.path.join(os.path.dirname(d), "intgrad"),
+                                                str(vid), 0, xs.shape[4], xs.shape[3])
+                if rise_heat is not None:
+                    for kind in ("freeze", "reverse"):
+                        viz.create_image_arrays(xs, rise_heat[j], tmask, j, kind, os.path.join(os.path.dirname(d), "rise"),
                                                 str(vid), 0, xs.shape[4], xs.shape[3])
                 if flavour != "smth":
                     import mask as _mask
@@ -191,8 +222,12 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
         if do_intgrad:
             with open(os.path.join(results_path, gname.replace("GradCam", "IntGrad").replace(os.sep, "_")), "wb") as f:
                 pickle.dump(ig_results, f)
+        if do_rise:
+            with open(os.path.join(results_path, gname.replace("GradCam", "Rise").replace(os.sep, "_")), "wb") as f:
+                pickle.dump(rise_results, f)
     find_masks_impl.last_results = (time_results, cam_results)
     find_masks_impl.last_ig_results = ig_results
+    find_masks_impl.last_rise_results = rise_results
     return masks
 
 

@@ -65,6 +65,7 @@ class CLSTMConfig(Structure):
 _P = c_void_p
 _I = c_int
 _F = c_float
+_U = ctypes.c_uint
 
 _SIGS = {
     "ivf_version": (c_int, []),
@@ -100,6 +101,10 @@ _SIGS = {
     "ivf_box_stage": (c_int, [_P] + [_I] * 5 + [_P, _P] + [_I] * 5 + [ctypes.c_longlong, _I, _P, _I, _P]),
     "ivf_box_select": (c_int, [_P, _P, _P] + [_I] * 7 + [_F] * 4 + [_P] * 5),
     "ivf_box_drop": (c_int, [_P, _P] + [_I] * 7 + [_P, _P]),
+    # csrc/rise_ops.hip (RISE random-mask saliency, documented extension)
+    "ivf_rise_masks": (c_int, [_U, _U] + [_I] * 5 + [_P, _P]),
+    "ivf_rise_stage": (c_int, [_P] + [_I] * 5 + [_P, _P] + [_I] * 4 + [_U, _U, ctypes.c_longlong, _I, _P, _I, _P]),
+    "ivf_rise_reduce": (c_int, [_P, _P, _I, _I, _U, _U] + [_I] * 3 + [_P] * 4),
     # csrc/ig_ops.hip (Integrated Gradients, documented extension)
     "ivf_ig_stage": (c_int, [_P, _I, _P, _F, _P] + [_I] * 5 + [ctypes.c_longlong, _I, _P, _I, _P]),
     "ivf_ig_accumulate": (c_int, [_P, _I, _P, _I, ctypes.c_longlong, _I, _P] + [_I] * 4 + [_P]),
@@ -149,6 +154,7 @@ _SIGS = {
     "ivf_i3d_ig": (c_int, [_P, _P, _I, _P, _I, _P, _F, _P, _P, _I] + [_P] * 7),
     "ivf_i3d_ig_path_scores": (c_int, [_P, _P, _I, _P, _I, _P, _F, _P, _I, _P, _P]),
     "ivf_i3d_box_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 5 + [_P, _P]),
+    "ivf_i3d_rise_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_U, _U, _P, _P]),
     "ivf_i3d_gradcam": (c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "ivf_i3d_gradcam_layer": (c_int, [_P, _P, _I, _P, c_char_p, _I, _I, _I, _P, _P, _P]),
     "ivf_i3d_conv_flops_per_clip": (ctypes.c_double, [_P]),
@@ -187,6 +193,7 @@ _SIGS = {
     "ivf_clstm_ig": (c_int, [_P, _P, _I, _P, _I, _P, _F, _P, _P, _I] + [_P] * 7),
     "ivf_clstm_ig_path_scores": (c_int, [_P, _P, _I, _P, _I, _P, _F, _P, _I, _P, _P]),
     "ivf_clstm_box_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 5 + [_P, _P]),
+    "ivf_clstm_rise_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_U, _U, _P, _P]),
     "ivf_clstm_gradcam_reduce": (c_int, [_P, _P, POINTER(c_int), _I, _P, _P, _I, _I, _I, _I, _P]),
     "ivf_clstm_set_cam_steps": (c_int, [_P, POINTER(c_int), _I]),
     "ivf_clstm_gradcam": (c_int, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),

@@ -243,8 +243,14 @@ class MaskSearch:
                  lr=0.2, grad_cam_type="guessed", do_gradcam=True, run_temp_mask=True,
                  normalize_per_frame=True, gradcam_size=None, mask_mode="central", max_mask_length=None,
                  mask_grid=None, mask_sigma=None, lam3=None, max_box=None, do_intgrad=False, ig_steps=32,
-                 ig_baseline="frozen"):
-        """do_intgrad (an extension without a counterpart in the reference): also run Integrated Gradients
+                 ig_baseline="frozen", do_rise=False, rise_masks=1024, rise_p=0.5, rise_grid=None, rise_sigma=None,
+                 rise_seed=0):
+        """do_rise (an extension without a counterpart in the reference): also run RISE random-mask saliency
+        of the target's score -- rise_masks random masks on rise_grid (gt, gh, gw) (default (min(T, 8),) + the spatial
+        grid of 'spacetime'), each cell frozen with probability rise_p, blurred by rise_sigma input pixels, drawn from
+        rise_seed; run() then also returns rise_map [b,T,H,W], rise_cells, rise_count [b,gt,gh,gw], rise_frames [b,T]
+        and rise_mean_drop [b].  The perturbation is the per-pixel freeze only.
+        do_intgrad (an extension without a counterpart in the reference): also run Integrated Gradients
         of the target's score with ig_steps midpoint nodes from the ig_baseline ('frozen': every frame = frame 0, the
         fully frozen clip of mask.py:123-128; 'constant': black); run() then also returns ig_map [b,T,H,W], ig_frames
         [b,T], ig_abs_frames, ig_total, ig_gap and ig_score_base [b].
@@ -273,6 +279,11 @@ class MaskSearch:
         self.do_intgrad, self.ig_steps, self.ig_baseline = bool(do_intgrad), ig_steps, ig_baseline   # read only when on
         if self.do_intgrad and ig_baseline not in ("frozen", "constant"):
             raise L.IvfError(f"ig_baseline must be 'frozen' or 'constant', got {ig_baseline!r}")
+        self.do_rise = bool(do_rise)                                                                  # read only when on
+        self.rise_masks, self.rise_p, self.rise_grid = rise_masks, rise_p, rise_grid
+        self.rise_sigma, self.rise_seed = rise_sigma, rise_seed
+        if self.do_rise and mask_type != "freeze":
+            raise L.IvfError("RISE perturbs by freezing only")
 
     def run(self, x, labels, want_traj=False):
         """x [b,C,T,H,W] float32 on the GPU, labels [b] ints.  Returns a dict of device
@@ -319,6 +330,14 @@ class MaskSearch:
             for k in ("ig_map", "ig_frames", "ig_abs_frames", "ig_total", "ig_gap"):
                 out[k] = r[k]
             out["ig_score_base"] = r["score_base"]
+        if self.do_rise:
+            grid = self.rise_grid
+            if grid is None:
+                grid = (min(x.shape[2], 8),) + self.st_grid(x)
+            r = eng.rise(x, target, n_masks=self.rise_masks, p=self.rise_p, grid=grid, sigma=self.rise_sigma,
+                         seed=self.rise_seed)
+            for k in ("rise_map", "rise_cells", "rise_count", "rise_frames", "rise_mean_drop"):
+                out[k] = r[k]
         return out
 
 
