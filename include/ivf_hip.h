@@ -270,6 +270,48 @@ int ivf_rise_stage(const float* x, int b, int C, int T, int H, int W, const floa
 int ivf_rise_reduce(const float* scores, const float* orig, int b, int n, unsigned seed, unsigned thresh, int gt, int gh,
                     int gw, float* cells, int* count, float* mean_drop, ivf_stream_t stream);
 
+/* ------------------------------------------------------------------ SmoothGrad, SmoothGrad^2, VarGrad (csrc/smoothgrad_ops.hip)
+ * An EXTENSION with no counterpart in the reference (Smilkov et al. 2017, Hooker et al. 2019): n noisy
+ * samples x + sigma z_k of a clip x [b,C,T,HW], one forward and backward each, and per input element the first two
+ * moments of g = d score / d input over the samples.  The (clip, sample) rows are numbered g = clip * n + k.
+ * Noise: one standard normal per sample k and element e = (c T + t) HW + px (the NCTHW index inside ONE clip, so it is
+ * the same for every clip and either staged layout), C T HW <= 2^31 - 1, all hash arithmetic uint32 and wrapping, fmix32
+ * as in the RISE section above:
+ *   key = fmix32(seed + 0x9E3779B9 (k + 1));  a = fmix32(key ^ (0x85EBCA77 (e + 1)));  h2 = fmix32(a + 0x9E3779B9)
+ *   u1 = (2 (a >> 9) + 1) 2^-24 in (0,1);  u2 = (h2 >> 8) 2^-24 in [0,1)          (both exact in fp32)
+ *   z = sqrtf(-2 logf(u1)) * cospif(2 u2),  |z| <= sqrt(48 ln 2) = 5.768
+ * one hash pair per element, no sin / cos pairing.  No entry stores the noise: it is regenerated.  No float atomics;
+ * every sum has a fixed order, so a clip's results depend neither on the batch it ran in nor on how the rows were cut
+ * into windows.
+ *
+ * Explicit z of samples [first_k, first_k + count) into z_out [count,C,T,HW]. */
+int ivf_sg_noise(unsigned seed, int first_k, int count, int C, int T, int HW, float* z_out, ivf_stream_t stream);
+/* sigma_out [b] = level * (max(x_clip) - min(x_clip)), one fp32 subtraction and one fp32 multiplication, computed on the
+ * device; level finite and >= 0; a NaN element is skipped by the min and the max. */
+int ivf_sg_range(const float* x, int b, int C, int T, int HW, float level, float* sigma_out, ivf_stream_t stream);
+/* Rows [first, first+count) into out; row j is clip (first+j)/n at sample (first+j)%n, each element
+ * fmaf(sigma[clip], z, x): equal to x where sigma == 0 (x == -0.0 becomes +0.0).  layout as the mask kernels name it: 0
+ * NCTHW [count,C,T,HW] (16-byte accesses when HW % 4 == 0 and x, out are 16-byte aligned), 4 16-byte channels-last pixels
+ * [count,T,HW,4] (C <= 4, out 16-byte aligned, pad lanes written +0.0). */
+int ivf_sg_stage(const float* x, const float* sigma, int b, int C, int T, int HW, int n, unsigned seed, long long first,
+                 int count, float* out, int layout, ivf_stream_t stream);
+/* G1, G2 [b,C,T,HW] (NCTHW, zeroed by the caller once per call) += the window's rows of din (layout as above, row j the
+ * gradient of row first+j): per element G1 = G1 + g and G2 = fmaf(g, g, G2) over the window's rows of its clip, k
+ * ascending, din read once for both.  Pad lanes of din are never read into a result. */
+int ivf_sg_accumulate(const float* din, int layout, int n, long long first, int count, float* G1, float* G2, int b, int C,
+                      int T, int HW, ivf_stream_t stream);
+/* Every operation rounded once in the order written, c ascending from +0.0:
+ *   sg_map [b,T,HW] = sum_c |G1 / n|;  sq_map = sum_c G2 / n;  var_map = sum_c (G2 - G1 * (G1 / n)) / (n - 1), 0.0 at n == 1
+ * sg_frames, sq_frames, var_frames [b,T] = sum_px of each map in the order of ivf_ig_finish (thread-order partial sums, a
+ * wave64 shuffle tree, then the waves in order).  n <= 2^24.  var_map cancels where the gradient hardly moves under
+ * the noise and may come out slightly negative there; nothing is clamped. */
+int ivf_sg_finish(const float* G1, const float* G2, int n, int b, int C, int T, int HW, float* sg_map, float* sq_map,
+                  float* var_map, float* sg_frames, float* sq_frames, float* var_frames, ivf_stream_t stream);
+/* Bytes of caller-owned scratch of ivf_{i3d,clstm}_smoothgrad for b clips and n samples: G1, G2 (b C T HW floats each),
+ * sigma (b floats), the per-row targets (b n ints), the row scores (b n floats), in that order, each piece rounded up to
+ * 256 bytes; 0 with the message set for bad dims. */
+size_t ivf_sg_workspace_bytes(int b, int C, int T, int HW, int n);
+
 /* Clip ingest: the arithmetic of ImLoader.__getitem__ /
  * KTHImLoader.__getitem__ after the JPEG decode (data_loader_jpg.py:29-37,
  * data_loader_kth.py:25-44): uint8 frames [B][T][H][W][C] -> float32 (exact), permuted to
@@ -585,6 +627,17 @@ int ivf_i3d_ig(ivf_i3d_t* net, const float* x, int b, const int* target, int bas
 int ivf_i3d_ig_path_scores(ivf_i3d_t* net, const float* x, int b, const int* target, int base_kind, const float* base,
                            float base_value, const float* alpha, int K, float* scores, ivf_stream_t stream);
 
+/* SmoothGrad, SmoothGrad^2 and VarGrad of b clips through this plan (extension, see ivf_sg_*): ivf_sg_range, then the
+ * b*n (clip, sample) rows in chunks of the plan's B rows across clip boundaries (ivf_sg_stage -> forward -> backward ->
+ * ivf_sg_accumulate), then ivf_sg_finish; b may exceed B.  The score is what ivf_i3d_backward differentiates (target
+ * [b]).  sg_map, sq_map, var_map [b,T,HW]; sg_frames, sq_frames, var_frames [b,T]; sample_scores [b,n] and sigma [b]
+ * (both optional): the score of every sample and the noise scale of every clip; ws = ivf_sg_workspace_bytes(b, C, T,
+ * H*W, n) bytes from the caller, 256-byte aligned.  n = 1, level = 0 is the plain gradient map sum_c |d score / d x|.
+ * One stream, no host synchronisation, no allocation. */
+int ivf_i3d_smoothgrad(ivf_i3d_t* net, const float* x, int b, const int* target, int n, float level, unsigned seed,
+                       float* sg_map, float* sq_map, float* var_map, float* sg_frames, float* sq_frames,
+                       float* var_frames, float* sample_scores, float* sigma, void* ws, ivf_stream_t stream);
+
 /* GradCamVideo.__call__ for archType "I3D" / target layer Mixed_5c,
  * grad_cam_videos.py:64-142, for b clips.  target[b] (device) selects the class;
  * cam [b,T'*(T/T'),out_h,out_w] (input_spatial_size, grad_cam_videos.py:54-57);
@@ -690,6 +743,10 @@ int ivf_clstm_ig(ivf_clstm_t* net, const float* x, int b, const int* target, int
                float* abs_frames, float* total, float* path_scores, void* ws, ivf_stream_t stream);
 int ivf_clstm_ig_path_scores(ivf_clstm_t* net, const float* x, int b, const int* target, int base_kind, const float* base,
                            float base_value, const float* alpha, int K, float* scores, ivf_stream_t stream);
+/* ivf_i3d_smoothgrad with the ConvLSTM backbone (rows staged NCTHW; the score is what ivf_clstm_backward differentiates). */
+int ivf_clstm_smoothgrad(ivf_clstm_t* net, const float* x, int b, const int* target, int n, float level, unsigned seed,
+                         float* sg_map, float* sq_map, float* var_map, float* sg_frames, float* sq_frames,
+                         float* var_frames, float* sample_scores, float* sigma, void* ws, ivf_stream_t stream);
 
 /* Grad-CAM on the ConvLSTM's pooled layer outputs, stored [B,T,hid,plane] (plane = Hp*Wp), fp32:
  * weights[b,c] = mean over (selected steps, plane) of grad (grad_cam_videos.py:98), cam[b,e,:] =

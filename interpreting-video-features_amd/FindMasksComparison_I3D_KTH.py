@@ -20,7 +20,8 @@ _state = {"sub_dir": "run0"}
 def find_masks(dat_loader, model, config, lam1, lam2, N, ita=1, maskType="gradient", temporalMaskType="freeze",
                classOI=None, verbose=True, maxMaskLength=None, doGradCam=False, runTempMask=True, maskGrid=None,
                maskSigma=None, lam3=None, maxBox=None, doIntGrad=False, igSteps=32, igBaseline="frozen", doRise=False,
-               riseMasks=1024, riseProb=0.5, riseGrid=None, riseSigma=None, riseSeed=0):
+               riseMasks=1024, riseProb=0.5, riseGrid=None, riseSigma=None, riseSeed=0, doSmoothGrad=False, sgSamples=32,
+               sgLevel=0.15, sgSeed=0):
     """KTH:126-380.  maskType 'combi': the exhaustive one-blob search (KTH:138-142), masks of length <=
     maxMaskLength; 'spacetime' (an extension, no counterpart in the reference): a mask per frame and cell of a
     maskGrid (gh, gw) grid, blurred by maskSigma input pixels, lam3 on the spatial TV term, records with 'st_mask';
@@ -34,14 +35,19 @@ def find_masks(dat_loader, model, config, lam1, lam2, N, ita=1, maskType="gradie
     doRise (an extension as well, whatever the maskType; freeze only) also runs RISE random-mask saliency -- riseMasks
     random masks on riseGrid (gt, gh, gw), each cell frozen with probability riseProb, blurred by riseSigma input pixels,
     drawn from riseSeed, forward passes only -- and writes a further pickle of records with 'RiseHeatMap' [T,H,W],
-    'RiseCells' and 'RiseCount' [gt,gh,gw], 'RiseFrames' [T], 'rise_mean_drop', 'n_masks', 'p', 'seed'."""
+    'RiseCells' and 'RiseCount' [gt,gh,gw], 'RiseFrames' [T], 'rise_mean_drop', 'n_masks', 'p', 'seed'.
+    doSmoothGrad (an extension as well, whatever the maskType) also runs SmoothGrad, SmoothGrad^2 and VarGrad -- sgSamples
+    noisy copies of the clip, noise of standard deviation sgLevel * (max - min) of the clip drawn from sgSeed, one forward
+    and backward each -- and writes a further pickle of records with 'SGHeatMap', 'SGSqHeatMap', 'SGVarHeatMap' [T,H,W],
+    'SGFrames' [T], 'sigma', 'n_samples', 'level', 'seed'."""
     return ivf_find_masks.find_masks_impl(
         dat_loader, model, config, lam1, lam2, N, temporalMaskType, classOI, verbose, doGradCam, runTempMask,
         flavour="kth", sub_dir=_state["sub_dir"], gradcam_size=(RESIZE_SIZE_HEIGHT, RESIZE_SIZE_WIDTH),
         mask_mode=maskType if maskType in ("combi", "spacetime", "stcombi") else "central",
         max_mask_length=maxMaskLength, mask_grid=maskGrid, mask_sigma=maskSigma, lam3=lam3, max_box=maxBox,
         do_intgrad=doIntGrad, ig_steps=igSteps, ig_baseline=igBaseline, do_rise=doRise, rise_masks=riseMasks,
-        rise_p=riseProb, rise_grid=riseGrid, rise_sigma=riseSigma, rise_seed=riseSeed)
+        rise_p=riseProb, rise_grid=riseGrid, rise_sigma=riseSigma, rise_seed=riseSeed, do_smoothgrad=doSmoothGrad,
+        sg_samples=sgSamples, sg_level=sgLevel, sg_seed=sgSeed)
 
 
 def build_model(config, args, device):

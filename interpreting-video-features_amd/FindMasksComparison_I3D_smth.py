@@ -24,7 +24,8 @@ _state = {"sub_dir": "run0"}
 def find_masks(dat_loader, model, hyper_params, lam1, lam2, N, maskType="gradient", temporalMaskType="freeze",
                classOI=None, verbose=True, maxMaskLength=None, doGradCam=False, runTempMask=True, maskGrid=None,
                maskSigma=None, lam3=None, maxBox=None, doIntGrad=False, igSteps=32, igBaseline="frozen", doRise=False,
-               riseMasks=1024, riseProb=0.5, riseGrid=None, riseSigma=None, riseSeed=0):
+               riseMasks=1024, riseProb=0.5, riseGrid=None, riseSigma=None, riseSeed=0, doSmoothGrad=False, sgSamples=32,
+               sgLevel=0.15, sgSeed=0):
     """smth:125-315.  maskType 'combi' runs the exhaustive one-blob search over masks of length <= maxMaskLength
     (smth:137-141, no gradient descent; N is unused); any other maskType keeps the gradient search from
     init_mask(mode="central"), which the reference hard-codes (smth:190).  maskType 'spacetime' (an extension, no
@@ -39,7 +40,11 @@ def find_masks(dat_loader, model, hyper_params, lam1, lam2, N, maskType="gradien
     doRise (an extension as well, whatever the maskType; freeze only) also runs RISE random-mask saliency -- riseMasks
     random masks on riseGrid (gt, gh, gw), each cell frozen with probability riseProb, blurred by riseSigma input pixels,
     drawn from riseSeed, forward passes only -- and writes a further pickle of records with 'RiseHeatMap' [T,H,W],
-    'RiseCells' and 'RiseCount' [gt,gh,gw], 'RiseFrames' [T], 'rise_mean_drop', 'n_masks', 'p', 'seed'."""
+    'RiseCells' and 'RiseCount' [gt,gh,gw], 'RiseFrames' [T], 'rise_mean_drop', 'n_masks', 'p', 'seed'.
+    doSmoothGrad (an extension as well, whatever the maskType) also runs SmoothGrad, SmoothGrad^2 and VarGrad -- sgSamples
+    noisy copies of the clip, noise of standard deviation sgLevel * (max - min) of the clip drawn from sgSeed, one forward
+    and backward each -- and writes a further pickle of records with 'SGHeatMap', 'SGSqHeatMap', 'SGVarHeatMap' [T,H,W],
+    'SGFrames' [T], 'sigma', 'n_samples', 'level', 'seed'."""
     return ivf_find_masks.find_masks_impl(
         dat_loader, model, hyper_params, lam1, lam2, N, temporalMaskType, classOI, verbose, doGradCam,
         runTempMask, flavour="smth", sub_dir=_state["sub_dir"],
@@ -47,7 +52,8 @@ def find_masks(dat_loader, model, hyper_params, lam1, lam2, N, maskType="gradien
         mask_mode=maskType if maskType in ("combi", "spacetime", "stcombi") else "central",
         max_mask_length=maxMaskLength, mask_grid=maskGrid, mask_sigma=maskSigma, lam3=lam3, max_box=maxBox,
         do_intgrad=doIntGrad, ig_steps=igSteps, ig_baseline=igBaseline, do_rise=doRise, rise_masks=riseMasks,
-        rise_p=riseProb, rise_grid=riseGrid, rise_sigma=riseSigma, rise_seed=riseSeed)
+        rise_p=riseProb, rise_grid=riseGrid, rise_sigma=riseSigma, rise_seed=riseSeed, do_smoothgrad=doSmoothGrad,
+        sg_samples=sgSamples, sg_level=sgLevel, sg_seed=sgSeed)
 
 
 def main(argv=None):

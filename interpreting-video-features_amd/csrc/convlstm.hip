@@ -1375,6 +1375,19 @@ extern "C" int ivf_clstm_ig_path_scores(ivf_clstm_t* net, const float* x, int b,
                             (hipStream_t)stream);
 }
 
+// SmoothGrad / SmoothGrad^2 / VarGrad (smoothgrad_ops.hip): run_smoothgrad on this plan; scratch from the caller.
+extern "C" int ivf_clstm_smoothgrad(ivf_clstm_t* net, const float* x, int b, const int* target, int n, float level,
+                                    unsigned seed, float* sg_map, float* sq_map, float* var_map, float* sg_frames,
+                                    float* sq_frames, float* var_frames, float* sample_scores, float* sigma, void* ws,
+                                    ivf_stream_t stream) {
+  IVF_PROPAGATE(clstm_ready(net, 1));
+  IVF_CHECK_ARG(x && target && sg_map && sq_map && var_map && sg_frames && sq_frames && var_frames && ws,
+                "clstm_smoothgrad: null pointer");
+  IVF_CHECK_ARG(b > 0 && n > 0, "clstm_smoothgrad: bad batch %d or sample count %d", b, n);
+  return run_smoothgrad(backbone(net), x, b, target, n, level, seed, sg_map, sq_map, var_map, sg_frames, sq_frames,
+                        var_frames, sample_scores, sigma, ws, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- Grad-CAM (grad_cam_videos.py:64-142, archType "CLSTM")
 
 static int cam_steps_from(const int* steps, int n_steps, int T, CamSteps* st) {

@@ -930,6 +930,19 @@ extern "C" int ivf_i3d_ig_path_scores(ivf_i3d_t* net, const float* x, int b, con
                             (hipStream_t)stream);
 }
 
+// SmoothGrad / SmoothGrad^2 / VarGrad (smoothgrad_ops.hip): run_smoothgrad on this plan; scratch from the caller.
+extern "C" int ivf_i3d_smoothgrad(ivf_i3d_t* net, const float* x, int b, const int* target, int n, float level,
+                                  unsigned seed, float* sg_map, float* sq_map, float* var_map, float* sg_frames,
+                                  float* sq_frames, float* var_frames, float* sample_scores, float* sigma, void* ws,
+                                  ivf_stream_t stream) {
+  IVF_PROPAGATE(check_ready(net, 1));
+  IVF_CHECK_ARG(x && target && sg_map && sq_map && var_map && sg_frames && sq_frames && var_frames && ws,
+                "i3d_smoothgrad: null pointer");
+  IVF_CHECK_ARG(b > 0 && n > 0, "i3d_smoothgrad: bad batch %d or sample count %d", b, n);
+  return run_smoothgrad(backbone(net), x, b, target, n, level, seed, sg_map, sq_map, var_map, sg_frames, sq_frames,
+                        var_frames, sample_scores, sigma, ws, (hipStream_t)stream);
+}
+
 extern "C" int ivf_i3d_gradcam(ivf_i3d_t* net, const float* x, int b, const int* target, int per_frame,
                                int out_h, int out_w, float* cam, float* probs, ivf_stream_t stream) {
   IVF_PROPAGATE(check_ready(net, b));

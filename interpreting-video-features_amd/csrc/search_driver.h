@@ -265,4 +265,49 @@ static int run_ig(const Backbone& v, const float* x, int b, const int* target, i
   return ivf_ig_finish(x, base_kind, base, base_value, Gsum, b, v.C, v.T, v.HW, ig_map, frames, abs_frames, total_out, s);
 }
 
+// ---------------------------------------------------------------- SmoothGrad / SmoothGrad^2 / VarGrad (smoothgrad_ops.hip)
+// An extension without a counterpart in the reference.  Its scratch belongs to the CALLER (ivf_sg_workspace_bytes), so
+// no plan's workspace size or carve order moves.
+struct SgScratch {
+  size_t g1 = 0, g2 = 0, sigma = 0, rowt = 0, score = 0;
+
+  // byte offsets of the pieces, each 256-byte aligned; returns the total.  per_clip = C * T * HW.
+  size_t carve(size_t b, size_t per_clip, size_t n) {
+    Bump256 a;
+    g1 = a.take(b * per_clip * 4);
+    g2 = a.take(b * per_clip * 4);
+    sigma = a.take(b * 4);
+    rowt = a.take(b * n * 4);
+    score = a.take(b * n * 4);
+    return a.top;
+  }
+};
+
+// The two gradient moments of b clips under n noisy samples each: range -> zero G1 / G2 -> per-row targets, then per
+// chunk of the plan's B rows stage -> forward -> backward -> accumulate, then finish.  sample_scores [b,n] and sigma [b]
+// (both optional): the scores the backward writes and the noise scale of each clip.  `ws`: the caller's
+// ivf_sg_workspace_bytes(b, C, T, HW, n) bytes.  One stream, no host synchronisation, no allocation.
+static int run_smoothgrad(const Backbone& v, const float* x, int b, const int* target, int n, float level, unsigned seed,
+                          float* sg_map, float* sq_map, float* var_map, float* sg_frames, float* sq_frames,
+                          float* var_frames, float* sample_scores, float* sigma_out, void* ws, hipStream_t s) {
+  SgScratch c;
+  const size_t per_clip = (size_t)v.C * v.T * v.HW;
+  c.carve((size_t)b, per_clip, (size_t)n);
+  float *G1 = (float*)((char*)ws + c.g1), *G2 = (float*)((char*)ws + c.g2);
+  float* sigma = sigma_out ? sigma_out : (float*)((char*)ws + c.sigma);
+  int* rowt = (int*)((char*)ws + c.rowt);
+  float* score = sample_scores ? sample_scores : (float*)((char*)ws + c.score);
+  IVF_PROPAGATE(ivf_sg_range(x, b, v.C, v.T, v.HW, level, sigma, s));
+  IVF_CHECK_HIP(hipMemsetAsync(G1, 0, (size_t)b * per_clip * 4, s));
+  IVF_CHECK_HIP(hipMemsetAsync(G2, 0, (size_t)b * per_clip * 4, s));
+  IVF_PROPAGATE(ig_row_targets(target, b, n, rowt, s));
+  IVF_PROPAGATE(for_each_chunk(v, (long long)b * n, [&](long long first, int cnt) -> int {
+    IVF_PROPAGATE(ivf_sg_stage(x, sigma, b, v.C, v.T, v.HW, n, seed, first, cnt, v.in, v.layout, s));
+    IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
+    IVF_PROPAGATE(v.backward(v.plan, cnt, rowt + first, score + first, s));
+    return ivf_sg_accumulate(v.din, v.layout, n, first, cnt, G1, G2, b, v.C, v.T, v.HW, s);
+  }));
+  return ivf_sg_finish(G1, G2, n, b, v.C, v.T, v.HW, sg_map, sq_map, var_map, sg_frames, sq_frames, var_frames, s);
+}
+
 }  // namespace ivf

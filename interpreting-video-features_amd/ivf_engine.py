@@ -496,6 +496,68 @@ class _Engine:
         return dict(rise_scores=scores, rise_cells=cells, rise_count=count, rise_mean_drop=mean_drop, score_x=score_x,
                     rise_map=self.st_expand(S, (gh, gw), sigma), rise_frames=frames)
 
+    # -------------------------------------------------------------- SmoothGrad / SmoothGrad^2 / VarGrad (extension)
+    def _sg_args(self, n_samples, level, seed):
+        """(n, level, seed) of a SmoothGrad call, checked"""
+        if not self._has_ig:
+            raise L.IvfError("SmoothGrad is built for the I3D and CLSTM plans only")
+        try:
+            n, seed, level = int(n_samples), int(seed), float(level)
+        except (TypeError, ValueError):
+            raise L.IvfError(f"n_samples, level, seed must be numbers, got {n_samples!r}, {level!r}, {seed!r}")
+        if not 1 <= n <= 2 ** 24:
+            raise L.IvfError(f"n_samples must be in [1, 2^24], got {n_samples}")
+        if not (math.isfinite(level) and level >= 0.0):
+            raise L.IvfError(f"level must be finite and >= 0, got {level}")
+        if not 0 <= seed < 2 ** 32:
+            raise L.IvfError(f"seed must be in [0, 2^32), got {seed}")
+        return n, level, seed
+
+    def sg_noise(self, n_samples=32, seed=0, first=0):
+        """The noise itself (ivf_sg_noise): z [n_samples,C,T,H,W] of samples first .. first + n_samples - 1, one standard
+        normal per (seed, sample, element).  The same for every clip."""
+        n, _, seed = self._sg_args(n_samples, 0.0, seed)
+        C, T, H, W = self.clip_shape
+        z = torch.empty(n, C, T, H, W, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().ivf_sg_noise(seed, int(first), n, C, T, H * W, L.ptr(z), L.stream()))
+        return z
+
+    def smoothgrad(self, x, target, n_samples=32, level=0.15, seed=0):
+        """SmoothGrad (Smilkov et al. 2017), SmoothGrad^2 and VarGrad (Hooker et al. 2019) of target[clip] on b clips
+        (ivf_*_smoothgrad; b may exceed max_batch): n_samples noisy copies x + sigma z_k of each clip, sigma = level *
+        (max(x_clip) - min(x_clip)), one forward and backward each.  Returns a dict of device tensors: sg_map (sum over
+        the channels of |mean gradient|), sq_map (of the mean squared gradient), var_map (of the unbiased variance of
+        the gradient; 0 at n_samples = 1) [b,T,H,W], sg_frames, sq_frames, var_frames [b,T], sample_scores [b,n],
+        sigma [b] and score_x [b] (the plan's ordinary forward).  n_samples = 1, level = 0 is plain gradient saliency."""
+        n, level, seed = self._sg_args(n_samples, level, seed)
+        x = self._clip(x, any_batch=True)
+        b = x.shape[0]
+        C, T, H, W = self.clip_shape
+        tgt = self._targets(target, b)
+        nbytes = L.lib().ivf_sg_workspace_bytes(b, C, T, H * W, n)
+        if nbytes == 0:
+            raise L.IvfError(L.lib().ivf_last_error().decode())
+        ws = self.__dict__.get("_sg_ws")
+        if ws is None or ws.numel() < nbytes:
+            self._sg_ws = None
+            with torch.cuda.device(self.device):
+                ws = self._sg_ws = _arena(nbytes, self.device)
+        dev = self.device
+        out = dict(sg_map=torch.empty(b, T, H, W, device=dev), sq_map=torch.empty(b, T, H, W, device=dev),
+                   var_map=torch.empty(b, T, H, W, device=dev), sg_frames=torch.empty(b, T, device=dev),
+                   sq_frames=torch.empty(b, T, device=dev), var_frames=torch.empty(b, T, device=dev),
+                   sample_scores=torch.empty(b, n, device=dev), sigma=torch.empty(b, device=dev))
+        with torch.cuda.device(dev):
+            L.check(self._fn("smoothgrad")(self._h, L.ptr(x), b, L.ptr(tgt), n, level, seed, L.ptr(out["sg_map"]),
+                                           L.ptr(out["sq_map"]), L.ptr(out["var_map"]), L.ptr(out["sg_frames"]),
+                                           L.ptr(out["sq_frames"]), L.ptr(out["var_frames"]),
+                                           L.ptr(out["sample_scores"]), L.ptr(out["sigma"]), L.ptr(ws), L.stream()))
+        idx = tgt.long().view(-1, 1)
+        out["score_x"] = torch.cat([self.forward(x[i:i + self.max_batch]).gather(1, idx[i:i + self.max_batch])
+                                    for i in range(0, b, self.max_batch)])[:, 0]
+        return out
+
     def argmax(self, probs):
         b = probs.shape[0]
         t = torch.empty(b, dtype=torch.int32, device=self.device)
@@ -757,7 +819,7 @@ class TFCLSTMEngine(_Engine):
     (mask/find_mask_kth.py:300-452, mask/gradcam.py:28-111) on libivf_hip's generic direct-convolution kernels
     (csrc/tf_clstm.hip).  Clips are NCTHW like everywhere else; `from_tf_layout` converts [B,T,H,W,C].
     The plan perturbs by freezing only and has no one-blob entry (the inherited `blob_scores` finds no symbol); `ig`,
-    `ig_path_scores` and the `rise*` entries refuse with IvfError."""
+    `ig_path_scores`, the `rise*` entries, `smoothgrad` and `sg_noise` refuse with IvfError."""
     _prefix = "tfclstm"
     _has_mode = False
     _has_st = False

@@ -48,8 +48,16 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                     results_path="results/", gradcam_size=None, write_files=True, device=None, visualise=True,
                     mask_mode="central", max_mask_length=None, blob_batch=32, mask_grid=None, mask_sigma=None, lam3=None,
                     max_box=None, do_intgrad=False, ig_steps=32, ig_baseline="frozen", do_rise=False, rise_masks=1024,
-                    rise_p=0.5, rise_grid=None, rise_sigma=None, rise_seed=0):
-    """do_rise (the drivers' doRise, an extension: DESIGN 14) also runs RISE random-mask saliency of the target's score
+                    rise_p=0.5, rise_grid=None, rise_sigma=None, rise_seed=0, do_smoothgrad=False, sg_samples=32,
+                    sg_level=0.15, sg_seed=0):
+    """do_smoothgrad (the drivers' doSmoothGrad, an extension: DESIGN 15) also runs SmoothGrad, SmoothGrad^2 and VarGrad
+    of the target's score (sg_samples noisy copies of each clip, noise of standard deviation sg_level * (max - min) of
+    the clip drawn from sg_seed, one forward and backward each) and writes a further list of records -- true_class,
+    pred_class, video_id, SGHeatMap, SGSqHeatMap, SGVarHeatMap [T,H,W], SGFrames [T], sigma, n_samples, level, seed -- to
+    a pickle named like the Grad-CAM one with SmoothGrad in place of GradCam; with the strips on, a further set of
+    heat-map strips (folder `smoothgrad` beside `combined`) blends sg_map scaled per frame; its plan holds at least
+    blob_batch clips so that the samples of a loader batch fill it.  Off, nothing changes.
+    do_rise (the drivers' doRise, an extension: DESIGN 14) also runs RISE random-mask saliency of the target's score
     (rise_masks masks on rise_grid (gt, gh, gw), each cell frozen with probability rise_p, blurred by rise_sigma input
     pixels, drawn from rise_seed; forward passes only) and writes a further list of records -- true_class, pred_class,
     video_id, RiseHeatMap [T,H,W], RiseCells [gt,gh,gw], RiseCount, RiseFrames [T], rise_mean_drop, n_masks, p, seed --
@@ -76,7 +84,7 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
     net = _unwrap(model)
     net.eval()                                                      # smth:145
     flt = _class_filter(classOI)
-    masks, time_results, cam_results, ig_results, rise_results = [], [], [], [], []
+    masks, time_results, cam_results, ig_results, rise_results, sg_results = [], [], [], [], [], []
     if write_files and not os.path.exists(results_path):
         os.makedirs(results_path)
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -94,7 +102,7 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
         if not keep:
             continue
         xs = x[keep].contiguous()
-        eng = net._engine_for(xs, min_batch=blob_batch) if mask_mode in ("combi", "stcombi") or do_rise \
+        eng = net._engine_for(xs, min_batch=blob_batch) if mask_mode in ("combi", "stcombi") or do_rise or do_smoothgrad \
             else net._engine_for(xs)
         search = ivf_search.MaskSearch(eng, lam1, lam2, N, temporalMaskType, threshold=0.9, lr=0.2,
                                        grad_cam_type=hyper_params.get("gradCamType", "guessed"),
@@ -103,9 +111,12 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                        max_mask_length=max_mask_length, mask_grid=mask_grid, mask_sigma=mask_sigma,
                                        lam3=lam3, max_box=max_box, do_intgrad=do_intgrad, ig_steps=ig_steps,
                                        ig_baseline=ig_baseline, do_rise=do_rise, rise_masks=rise_masks, rise_p=rise_p,
-                                       rise_grid=rise_grid, rise_sigma=rise_sigma, rise_seed=rise_seed)
+                                       rise_grid=rise_grid, rise_sigma=rise_sigma, rise_seed=rise_seed,
+                                       do_smoothgrad=do_smoothgrad, sg_samples=sg_samples, sg_level=sg_level,
+                                       sg_seed=sg_seed)
         res = search.run(xs, labels[keep])
-        host = {k: v.detach().cpu() for k, v in res.items() if k not in ("gradcam", "box_scores", "ig_map", "rise_map")}
+        host = {k: v.detach().cpu() for k, v in res.items()
+                if k not in ("gradcam", "box_scores", "ig_map", "rise_map", "sg_map", "sg_sq_map", "sg_var_map")}
         spacetime = runTempMask and mask_mode in ("spacetime", "stcombi")
         st_maps = eng.st_expand(res["st_mask"], search.st_grid(xs), mask_sigma) if spacetime and write_files and visualise \
             else None
@@ -129,6 +140,15 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                 pos = res["rise_map"].clamp_min(0.0)
                 top = pos.amax(dim=(2, 3), keepdim=True)
                 rise_heat = torch.where(top > 0, pos / torch.where(top > 0, top, torch.ones_like(top)), torch.zeros_like(pos))
+        sg_heat = None
+        if do_smoothgrad:
+            for k in ("sg_map", "sg_sq_map", "sg_var_map"):
+                host[k] = res[k].detach().cpu()
+            if runTempMask and write_files and visualise:
+                # as ig_heat: sg_map (non-negative) scaled to [0,1] per frame; a frame without a gradient stays all zero
+                pos = res["sg_map"].clamp_min(0.0)
+                top = pos.amax(dim=(2, 3), keepdim=True)
+                sg_heat = torch.where(top > 0, pos / torch.where(top > 0, top, torch.ones_like(top)), torch.zeros_like(pos))
         for j, bi in enumerate(keep):
             true_class = int(labels[bi])
             pred = int(host["pred_class"][j])
@@ -183,6 +203,15 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                      'RiseFrames': host["rise_frames"][j].numpy().astype(np.float32),
                                      'rise_mean_drop': float(host["rise_mean_drop"][j]),
                                      'n_masks': int(rise_masks), 'p': float(rise_p), 'seed': int(rise_seed)})
+            if do_smoothgrad:
+                sg_results.append({'true_class': true_class, 'pred_class': pred,
+                                   'video_id': int(vid) if flavour == "smth" else vid,
+                                   'SGHeatMap': host["sg_map"][j].numpy().astype(np.float32),
+                                   'SGSqHeatMap': host["sg_sq_map"][j].numpy().astype(np.float32),
+                                   'SGVarHeatMap': host["sg_var_map"][j].numpy().astype(np.float32),
+                                   'SGFrames': host["sg_frames"][j].numpy().astype(np.float32),
+                                   'sigma': float(host["sg_sigma"][j]), 'n_samples': int(sg_samples),
+                                   'level': float(sg_level), 'seed': int(sg_seed)})
             if runTempMask and write_files and visualise:
                 # smth:296-303 / KTH:354-367: heat-map strips with the mask dot row for both perturbation
                 # types (the dot row snaps a host copy: `tmask` keeps its sigmoid values, as the reference's
@@ -200,6 +229,11 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                     for kind in ("freeze", "reverse"):
                         viz.create_image_arrays(xs, rise_heat[j], tmask, j, kind, os.path.join(os.path.dirname(d), "rise"),
                                                 str(vid), 0, xs.shape[4], xs.shape[3])
+                if sg_heat is not None:
+                    for kind in ("freeze", "reverse"):
+                        viz.create_image_arrays(xs, sg_heat[j], tmask, j, kind,
+                                                os.path.join(os.path.dirname(d), "smoothgrad"), str(vid), 0, xs.shape[4],
+                                                xs.shape[3])
                 if flavour != "smth":
                     import mask as _mask
                     pert = st_pert[j] if st_pert is not None else _mask.perturb_sequence(xs, tmask, temporalMaskType)[j]
@@ -225,9 +259,13 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
         if do_rise:
             with open(os.path.join(results_path, gname.replace("GradCam", "Rise").replace(os.sep, "_")), "wb") as f:
                 pickle.dump(rise_results, f)
+        if do_smoothgrad:
+            with open(os.path.join(results_path, gname.replace("GradCam", "SmoothGrad").replace(os.sep, "_")), "wb") as f:
+                pickle.dump(sg_results, f)
     find_masks_impl.last_results = (time_results, cam_results)
     find_masks_impl.last_ig_results = ig_results
     find_masks_impl.last_rise_results = rise_results
+    find_masks_impl.last_sg_results = sg_results
     return masks
 
 

@@ -110,6 +110,13 @@ _SIGS = {
     "ivf_ig_accumulate": (c_int, [_P, _I, _P, _I, ctypes.c_longlong, _I, _P] + [_I] * 4 + [_P]),
     "ivf_ig_finish": (c_int, [_P, _I, _P, _F, _P] + [_I] * 4 + [_P] * 5),
     "ivf_ig_workspace_bytes": (c_size_t, [_I] * 5),
+    # csrc/smoothgrad_ops.hip (SmoothGrad / SmoothGrad^2 / VarGrad, documented extension)
+    "ivf_sg_noise": (c_int, [_U] + [_I] * 5 + [_P, _P]),
+    "ivf_sg_range": (c_int, [_P] + [_I] * 4 + [_F, _P, _P]),
+    "ivf_sg_stage": (c_int, [_P, _P] + [_I] * 5 + [_U, ctypes.c_longlong, _I, _P, _I, _P]),
+    "ivf_sg_accumulate": (c_int, [_P, _I, _I, ctypes.c_longlong, _I, _P, _P] + [_I] * 4 + [_P]),
+    "ivf_sg_finish": (c_int, [_P, _P] + [_I] * 5 + [_P] * 7),
+    "ivf_sg_workspace_bytes": (c_size_t, [_I] * 5),
     "ivf_clip_ingest_u8": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ivf_conv3d": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
     "ivf_bn_fold": (c_int, [_P, _P, _P, _P, _F, _P, _P, _I, _P]),
@@ -155,6 +162,7 @@ _SIGS = {
     "ivf_i3d_ig_path_scores": (c_int, [_P, _P, _I, _P, _I, _P, _F, _P, _I, _P, _P]),
     "ivf_i3d_box_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 5 + [_P, _P]),
     "ivf_i3d_rise_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_U, _U, _P, _P]),
+    "ivf_i3d_smoothgrad": (c_int, [_P, _P, _I, _P, _I, _F, _U] + [_P] * 10),
     "ivf_i3d_gradcam": (c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "ivf_i3d_gradcam_layer": (c_int, [_P, _P, _I, _P, c_char_p, _I, _I, _I, _P, _P, _P]),
     "ivf_i3d_conv_flops_per_clip": (ctypes.c_double, [_P]),
@@ -194,6 +202,7 @@ _SIGS = {
     "ivf_clstm_ig_path_scores": (c_int, [_P, _P, _I, _P, _I, _P, _F, _P, _I, _P, _P]),
     "ivf_clstm_box_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 5 + [_P, _P]),
     "ivf_clstm_rise_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_U, _U, _P, _P]),
+    "ivf_clstm_smoothgrad": (c_int, [_P, _P, _I, _P, _I, _F, _U] + [_P] * 10),
     "ivf_clstm_gradcam_reduce": (c_int, [_P, _P, POINTER(c_int), _I, _P, _P, _I, _I, _I, _I, _P]),
     "ivf_clstm_set_cam_steps": (c_int, [_P, POINTER(c_int), _I]),
     "ivf_clstm_gradcam": (c_int, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),

@@ -244,8 +244,12 @@ class MaskSearch:
                  normalize_per_frame=True, gradcam_size=None, mask_mode="central", max_mask_length=None,
                  mask_grid=None, mask_sigma=None, lam3=None, max_box=None, do_intgrad=False, ig_steps=32,
                  ig_baseline="frozen", do_rise=False, rise_masks=1024, rise_p=0.5, rise_grid=None, rise_sigma=None,
-                 rise_seed=0):
-        """do_rise (an extension without a counterpart in the reference): also run RISE random-mask saliency
+                 rise_seed=0, do_smoothgrad=False, sg_samples=32, sg_level=0.15, sg_seed=0):
+        """do_smoothgrad (an extension without a counterpart in the reference): also run SmoothGrad,
+        SmoothGrad^2 and VarGrad of the target's score -- sg_samples noisy copies of each clip, noise of standard
+        deviation sg_level * (max(clip) - min(clip)) drawn from sg_seed, one forward and backward each; run() then also
+        returns sg_map, sg_sq_map, sg_var_map [b,T,H,W], sg_frames [b,T] and sg_sigma [b].
+        do_rise (an extension without a counterpart in the reference): also run RISE random-mask saliency
         of the target's score -- rise_masks random masks on rise_grid (gt, gh, gw) (default (min(T, 8),) + the spatial
         grid of 'spacetime'), each cell frozen with probability rise_p, blurred by rise_sigma input pixels, drawn from
         rise_seed; run() then also returns rise_map [b,T,H,W], rise_cells, rise_count [b,gt,gh,gw], rise_frames [b,T]
@@ -284,6 +288,8 @@ class MaskSearch:
         self.rise_sigma, self.rise_seed = rise_sigma, rise_seed
         if self.do_rise and mask_type != "freeze":
             raise L.IvfError("RISE perturbs by freezing only")
+        self.do_smoothgrad = bool(do_smoothgrad)                                                      # read only when on
+        self.sg_samples, self.sg_level, self.sg_seed = sg_samples, sg_level, sg_seed
 
     def run(self, x, labels, want_traj=False):
         """x [b,C,T,H,W] float32 on the GPU, labels [b] ints.  Returns a dict of device
@@ -338,6 +344,10 @@ class MaskSearch:
                          seed=self.rise_seed)
             for k in ("rise_map", "rise_cells", "rise_count", "rise_frames", "rise_mean_drop"):
                 out[k] = r[k]
+        if self.do_smoothgrad:
+            r = eng.smoothgrad(x, target, n_samples=self.sg_samples, level=self.sg_level, seed=self.sg_seed)
+            out["sg_map"], out["sg_sq_map"], out["sg_var_map"] = r["sg_map"], r["sq_map"], r["var_map"]
+            out["sg_frames"], out["sg_sigma"] = r["sg_frames"], r["sigma"]
         return out
 
 
