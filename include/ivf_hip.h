@@ -270,6 +270,38 @@ int ivf_rise_stage(const float* x, int b, int C, int T, int H, int W, const floa
 int ivf_rise_reduce(const float* scores, const float* orig, int b, int n, unsigned seed, unsigned thresh, int gt, int gh,
                     int gw, float* cells, int* count, float* mean_drop, ivf_stream_t stream);
 
+/* ------------------------------------------------------------------ Shapley value sampling (csrc/shapley_ops.hip)
+ * An EXTENSION with no counterpart in the reference (Castro et al. 2009, Strumbelj & Kononenko 2014): the
+ * players are the P = gt gh gw cells of a grid as in the RISE section above (1 <= gt <= T <= 64, 1 <= gh, gw <= 32, and
+ * P <= 4096), a coalition is the set of frozen cells, its value the class score of the clip frozen per pixel by that
+ * binary mask.  Permutation k freezes the cells one after another in the order of
+ *   rank_k[c] = #{c' : (h(seed,k,c'), c') < (h(seed,k,c), c)},     h = the hash of the RISE section (lexicographic
+ *   order: a hash tie falls to the lower cell index, so every row is a permutation of 0 .. P-1),
+ * and with antithetic = 1 an odd k is permutation k-1 (hashed as itself) reversed: rank_k[c] = P-1 - rank_{k-1}[c].
+ * Row j = 0 .. P of permutation k freezes the cells with rank_k[c] < j: row 0 is the clip, row P the fully frozen clip.
+ * The marginal of cell c is d_k[c] = s[k][rank_k[c]] - s[k][rank_k[c]+1] (> 0: freezing c lowers the score), and
+ * sum_c d_k[c] = s[k][0] - s[k][P] for every k.  The permutations are the same for every clip.
+ *
+ * Rank table of permutations [first_k, first_k+count) into ranks [count,P] (uint16; antithetic 0 or 1). */
+int ivf_shap_ranks(unsigned seed, int antithetic, int first_k, int count, int gt, int gh, int gw, unsigned short* ranks,
+                   ivf_stream_t stream);
+/* Rows [first, first+count) of the flattened (clip, permutation, prefix) list of b clips x [b,C,T,H,W] into p: row r is
+ * clip r / (n (P+1)), permutation (r / (P+1)) % n, prefix r % (P+1), of the n (P+1) rows a clip has; count <= 65535.
+ * ranks [n,P] on the device: the table of permutations 0 .. n-1 (ivf_shap_ranks, or the caller's own).  out_cpad, A_H,
+ * A_W as ivf_rise_stage.  The rows equal (==) what ivf_stmask_expand_fwd followed by ivf_stfreeze_fwd write for the
+ * row's explicit per-frame S (S[u][c] = 1 iff rank[c] < prefix, c in the temporal cell of frame u); neither S nor M is
+ * ever in memory. */
+int ivf_shap_stage(const float* x, int b, int C, int T, int H, int W, const float* A_H, const float* A_W, int gt, int gh,
+                   int gw, int n, const unsigned short* ranks, long long first, int count, float* p, int out_cpad,
+                   ivf_stream_t stream);
+/* The estimator from scores [b,n,P+1] and ranks [n,P], k ascending in plain fp32, one thread per (clip, cell), no
+ * atomics: cells [b,gt,gh,gw] = sum_k d_k / count, count (int) the number of terms; a term with a NaN score on either
+ * side (or a rank outside 0 .. P-1) is neither summed nor counted; cells is NaN where count == 0.  std_err = sqrt(sum_k
+ * (d_k - cells)^2 / (count - 1) / count), a second pass in the same order, NaN where count < 2.  total [b] = the mean of
+ * s[k][0] - s[k][P] over the permutations whose two end scores are finite (NaN if none): what the cells sum to. */
+int ivf_shap_reduce(const float* scores, const unsigned short* ranks, int b, int n, int gt, int gh, int gw, float* cells,
+                    float* std_err, int* count, float* total, ivf_stream_t stream);
+
 /* ------------------------------------------------------------------ SmoothGrad, SmoothGrad^2, VarGrad (csrc/smoothgrad_ops.hip)
  * An EXTENSION with no counterpart in the reference (Smilkov et al. 2017, Hooker et al. 2019): n noisy
  * samples x + sigma z_k of a clip x [b,C,T,HW], one forward and backward each, and per input element the first two
@@ -613,6 +645,12 @@ int ivf_i3d_box_scores(ivf_i3d_t* net, const float* x, int b, const int* target,
 int ivf_i3d_rise_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
                         int gt, int gh, int gw, int n, unsigned seed, unsigned thresh, float* scores,
                         ivf_stream_t stream);
+/* Scores of the n (P+1) Shapley rows of each of b clips (extension, see ivf_shap_*): scores [b,n,P+1] =
+ * probs[target[clip]] of the clip frozen per pixel by prefix j of permutation k (ranks [n,P] on the device), in chunks
+ * of the plan's B rows (ivf_shap_stage -> forward -> pick); b may exceed B.  One stream, no host synchronisation, no
+ * allocation, no scratch beyond scores. */
+int ivf_i3d_shap_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
+                        int gt, int gh, int gw, int n, const unsigned short* ranks, float* scores, ivf_stream_t stream);
 
 /* Integrated Gradients of b clips through this plan (extension, see ivf_ig_*): the b*K path points run in chunks of the
  * plan's B rows across clip boundaries (ivf_ig_stage -> forward -> backward -> ivf_ig_accumulate), then ivf_ig_finish;
@@ -730,6 +768,9 @@ int ivf_clstm_box_scores(ivf_clstm_t* net, const float* x, int b, const int* tar
 int ivf_clstm_rise_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
                           int gt, int gh, int gw, int n, unsigned seed, unsigned thresh, float* scores,
                           ivf_stream_t stream);
+/* ivf_i3d_shap_scores with the ConvLSTM backbone (rows staged NCTHW). */
+int ivf_clstm_shap_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
+                          int gt, int gh, int gw, int n, const unsigned short* ranks, float* scores, ivf_stream_t stream);
 
 /* Integrated Gradients of b clips through this plan (extension, see ivf_ig_*): the b*K path points run in chunks of the
  * plan's B rows across clip boundaries (ivf_ig_stage -> forward -> backward -> ivf_ig_accumulate), then ivf_ig_finish;

@@ -21,7 +21,7 @@ def find_masks(dat_loader, model, config, lam1, lam2, N, ita=1, maskType="gradie
                classOI=None, verbose=True, maxMaskLength=None, doGradCam=False, runTempMask=True, maskGrid=None,
                maskSigma=None, lam3=None, maxBox=None, doIntGrad=False, igSteps=32, igBaseline="frozen", doRise=False,
                riseMasks=1024, riseProb=0.5, riseGrid=None, riseSigma=None, riseSeed=0, doSmoothGrad=False, sgSamples=32,
-               sgLevel=0.15, sgSeed=0):
+               sgLevel=0.15, sgSeed=0, doShapley=False, shapPerms=64, shapGrid=None, shapSigma=None, shapSeed=0):
     """KTH:126-380.  maskType 'combi': the exhaustive one-blob search (KTH:138-142), masks of length <=
     maxMaskLength; 'spacetime' (an extension, no counterpart in the reference): a mask per frame and cell of a
     maskGrid (gh, gw) grid, blurred by maskSigma input pixels, lam3 on the spatial TV term, records with 'st_mask';
@@ -39,7 +39,12 @@ def find_masks(dat_loader, model, config, lam1, lam2, N, ita=1, maskType="gradie
     doSmoothGrad (an extension as well, whatever the maskType) also runs SmoothGrad, SmoothGrad^2 and VarGrad -- sgSamples
     noisy copies of the clip, noise of standard deviation sgLevel * (max - min) of the clip drawn from sgSeed, one forward
     and backward each -- and writes a further pickle of records with 'SGHeatMap', 'SGSqHeatMap', 'SGVarHeatMap' [T,H,W],
-    'SGFrames' [T], 'sigma', 'n_samples', 'level', 'seed'."""
+    'SGFrames' [T], 'sigma', 'n_samples', 'level', 'seed'.
+    doShapley (an extension as well, whatever the maskType; freeze only) also runs Shapley value sampling -- shapPerms
+    permutations of the cells of shapGrid (gt, gh, gw) (default (T, 1, 1): the frames are the players), blurred by
+    shapSigma input pixels, drawn from shapSeed, forward passes only, shapPerms (cells + 1) of them per clip -- and writes a
+    further pickle of records with 'ShapHeatMap' [T,H,W], 'ShapCells' and 'ShapStderr' [gt,gh,gw], 'ShapFrames' [T],
+    'shap_total', 'n_perms', 'seed'."""
     return ivf_find_masks.find_masks_impl(
         dat_loader, model, config, lam1, lam2, N, temporalMaskType, classOI, verbose, doGradCam, runTempMask,
         flavour="kth", sub_dir=_state["sub_dir"], gradcam_size=(RESIZE_SIZE_HEIGHT, RESIZE_SIZE_WIDTH),
@@ -47,7 +52,8 @@ def find_masks(dat_loader, model, config, lam1, lam2, N, ita=1, maskType="gradie
         max_mask_length=maxMaskLength, mask_grid=maskGrid, mask_sigma=maskSigma, lam3=lam3, max_box=maxBox,
         do_intgrad=doIntGrad, ig_steps=igSteps, ig_baseline=igBaseline, do_rise=doRise, rise_masks=riseMasks,
         rise_p=riseProb, rise_grid=riseGrid, rise_sigma=riseSigma, rise_seed=riseSeed, do_smoothgrad=doSmoothGrad,
-        sg_samples=sgSamples, sg_level=sgLevel, sg_seed=sgSeed)
+        sg_samples=sgSamples, sg_level=sgLevel, sg_seed=sgSeed, do_shapley=doShapley, shap_perms=shapPerms,
+        shap_grid=shapGrid, shap_sigma=shapSigma, shap_seed=shapSeed)
 
 
 def build_model(config, args, device):

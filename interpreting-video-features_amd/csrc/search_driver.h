@@ -214,6 +214,24 @@ static inline int run_rise_scores(const Backbone& v, const float* x, int b, cons
   });
 }
 
+// Shapley value sampling (shapley_ops.hip; an extension): run_rise_scores with the prefix staging -- per chunk
+// ivf_shap_stage -> forward -> blob_pick on the b * n * (P + 1) (clip, permutation, prefix) rows, ranks [n,P] the
+// caller's table; one stream, no host synchronisation, no allocation, no scratch beyond `scores`.
+static inline int run_shap_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,
+                                  const float* A_W, int gt, int gh, int gw, int H, int W, int n,
+                                  const unsigned short* ranks, float* scores, hipStream_t s) {
+  const long long per = (long long)n * ((long long)gt * gh * gw + 1);       // rows of one clip
+  if (per > 0x7fffffffLL) {
+    set_error("shap_scores: %lld rows per clip", per);
+    return IVF_ERR_BAD_ARG;
+  }
+  return for_each_chunk(v, b * per, [&](long long first, int cnt) -> int {
+    IVF_PROPAGATE(ivf_shap_stage(x, b, v.C, v.T, H, W, A_H, A_W, gt, gh, gw, n, ranks, first, cnt, v.in, v.layout, s));
+    IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
+    return blob_pick(v.probs, target, v.K, (int)per, first, cnt, scores, s);
+  });
+}
+
 // ---------------------------------------------------------------- Integrated Gradients (ig_ops.hip)
 // An extension without a counterpart in the reference.  Its scratch belongs to the CALLER (ivf_ig_workspace_bytes), so
 // no plan's workspace size or carve order moves.

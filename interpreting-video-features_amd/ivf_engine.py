@@ -558,6 +558,110 @@ class _Engine:
                                     for i in range(0, b, self.max_batch)])[:, 0]
         return out
 
+    # -------------------------------------------------------------- Shapley value sampling (extension)
+    def _shap_args(self, n_perms, grid, sigma, seed, antithetic=True):
+        """(gt, gh, gw, n, seed, antithetic, A_H, A_W) of a Shapley call, checked; grid None -> (T, 1, 1): the players
+        are the frames."""
+        if not self._has_st:
+            raise L.IvfError("Shapley value sampling is built for the I3D and CLSTM plans only")
+        C, T, H, W = self.clip_shape
+        if grid is None:
+            grid = (T, 1, 1)
+        try:
+            gt, gh, gw = (int(v) for v in grid)
+        except (TypeError, ValueError):
+            raise L.IvfError(f"grid must be (gt, gh, gw), got {grid!r}")
+        if not (1 <= gt <= T <= 64 and 1 <= gh <= 32 and 1 <= gw <= 32 and gt * gh * gw <= 4096):
+            raise L.IvfError(f"grid {(gt, gh, gw)}: need 1 <= gt <= T = {T} <= 64, 1 <= gh, gw <= 32 and at most 4096 cells")
+        try:
+            n, seed = int(n_perms), int(seed)
+        except (TypeError, ValueError):
+            raise L.IvfError(f"n_perms and seed must be integers, got {n_perms!r}, {seed!r}")
+        if not 1 <= n <= 2 ** 20:
+            raise L.IvfError(f"n_perms must be in [1, 2^20], got {n_perms}")
+        if not 0 <= seed < 2 ** 32:
+            raise L.IvfError(f"seed must be in [0, 2^32), got {seed}")
+        _, _, _, AH, AW = self._st_axes((gh, gw), sigma)
+        return gt, gh, gw, n, seed, int(bool(antithetic)), AH, AW
+
+    def shap_ranks(self, n_perms=64, grid=None, seed=0, antithetic=True, first=0):
+        """The sampled permutations themselves (ivf_shap_ranks): int16 [n_perms, gt gh gw] holding the uint16 rank
+        (0 .. P-1) of every cell in permutations first .. first + n_perms - 1; cell c is frozen from prefix rank + 1
+        on.  The same for every clip."""
+        gt, gh, gw, n, seed, anti, _, _ = self._shap_args(n_perms, grid, None, seed, antithetic)
+        ranks = torch.empty(n, gt * gh * gw, dtype=torch.int16, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().ivf_shap_ranks(seed, anti, int(first), n, gt, gh, gw, L.ptr(ranks), L.stream()))
+        return ranks
+
+    def shap_scores(self, x, target, n_perms=64, grid=None, sigma=None, seed=0, antithetic=True):
+        """Scores [b, n_perms, P+1] of target[clip]: entry [.., k, j] has the j cells of lowest rank in permutation k
+        frozen per pixel (expanded as st_expand expands a mask), so [.., 0] is the clip and [.., P] the fully frozen
+        clip: ivf_*_shap_scores, forward only, chunks of the plan's max_batch rows; b may exceed max_batch."""
+        gt, gh, gw, n, seed, anti, AH, AW = self._shap_args(n_perms, grid, sigma, seed, antithetic)
+        x = self._clip(x, any_batch=True)
+        b = x.shape[0]
+        tgt = self._targets(target, b)
+        ranks = self.shap_ranks(n, (gt, gh, gw), seed, anti)
+        scores = torch.empty(b, n, gt * gh * gw + 1, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(self._fn("shap_scores")(self._h, L.ptr(x), b, L.ptr(tgt), L.ptr(AH), L.ptr(AW), gt, gh, gw, n,
+                                            L.ptr(ranks), L.ptr(scores), L.stream()))
+        return scores
+
+    def shap_reduce(self, scores, grid=None, seed=0, antithetic=True):
+        """ivf_shap_reduce on scores [b,n,P+1] with the rank table of (grid, seed, antithetic): (cells [b,gt,gh,gw],
+        stderr, count int32, total [b])."""
+        s = L.f32c(scores)
+        L.require_gpu(s)
+        if s.dim() != 3:
+            raise L.IvfError(f"scores must be [b, n_perms, P+1], got {tuple(s.shape)}")
+        b, n, rows = s.shape
+        gt, gh, gw, n, seed, anti, _, _ = self._shap_args(n, grid, None, seed, antithetic)
+        if rows != gt * gh * gw + 1:
+            raise L.IvfError(f"scores {tuple(s.shape)} do not hold the {gt * gh * gw + 1} prefixes of grid {(gt, gh, gw)}")
+        ranks = self.shap_ranks(n, (gt, gh, gw), seed, anti)
+        cells = torch.empty(b, gt, gh, gw, device=s.device)
+        stderr = torch.empty(b, gt, gh, gw, device=s.device)
+        count = torch.empty(b, gt, gh, gw, dtype=torch.int32, device=s.device)
+        total = torch.empty(b, device=s.device)
+        with torch.cuda.device(s.device):
+            L.check(L.lib().ivf_shap_reduce(L.ptr(s), L.ptr(ranks), b, n, gt, gh, gw, L.ptr(cells), L.ptr(stderr),
+                                            L.ptr(count), L.ptr(total), L.stream()))
+        return cells, stderr, count, total
+
+    def shapley(self, x, target, n_perms=64, grid=None, sigma=None, seed=0, antithetic=True):
+        """Shapley values of the cells of grid = (gt, gh, gw) (default (T, 1, 1): the frames) under the per-pixel
+        freeze, by permutation sampling (Castro et al. 2009), for target[clip] on b clips, b may exceed max_batch:
+        along each of n_perms permutations the cells are frozen one after another, one forward per prefix (n_perms (P+1)
+        rows a clip); a cell's value is the mean score drop on its entry, > 0 where freezing it lowers the score.
+        antithetic: every odd permutation is the one before it reversed.  Returns a dict of device tensors: shap_scores
+        [b,n,P+1], shap_cells, shap_stderr (the standard error of the mean), shap_count (int32) [b,gt,gh,gw], shap_total
+        [b] (= mean of score(clip) - score(fully frozen clip), what the cells sum to), score_x [b] (the plan's ordinary
+        forward), shap_map [b,T,H,W] (the cells repeated over the frames of their temporal cell and expanded with
+        st_expand) and shap_frames [b,T] (a temporal cell's spatial sum shared equally among its frames: it sums to
+        the sum of the cells)."""
+        gt, gh, gw, n, seed, anti, AH, AW = self._shap_args(n_perms, grid, sigma, seed, antithetic)
+        x = self._clip(x, any_batch=True)
+        b = x.shape[0]
+        C, T, H, W = self.clip_shape
+        tgt = self._targets(target, b)
+        idx = tgt.long().view(-1, 1)
+        score_x = torch.cat([self.forward(x[i:i + self.max_batch]).gather(1, idx[i:i + self.max_batch])
+                             for i in range(0, b, self.max_batch)])[:, 0].contiguous()
+        scores = self.shap_scores(x, tgt, n, (gt, gh, gw), sigma, seed, anti)
+        cells, stderr, count, total = self.shap_reduce(scores, (gt, gh, gw), seed, anti)
+        kt = (torch.arange(T, device=self.device) * gt) // T
+        S = cells[:, kt].contiguous()                                   # [b,T,gh,gw]
+        share = 1.0 / torch.bincount(kt, minlength=gt).to(torch.float32)[kt]            # 1 / frames of the frame's cell
+        frames = torch.empty(b, T, device=self.device)
+        ah, aw = torch.ones(1, gh, device=self.device), torch.ones(1, gw, device=self.device)
+        with torch.cuda.device(self.device):                            # unit rows: the spatial sum per frame
+            L.check(L.lib().ivf_stmask_expand_fwd(L.ptr(S), L.ptr(ah), L.ptr(aw), L.ptr(frames), b, T, gh, gw, 1, 1,
+                                                  L.stream()))
+        return dict(shap_scores=scores, shap_cells=cells, shap_stderr=stderr, shap_count=count, shap_total=total,
+                    score_x=score_x, shap_map=self.st_expand(S, (gh, gw), sigma), shap_frames=frames * share)
+
     def argmax(self, probs):
         b = probs.shape[0]
         t = torch.empty(b, dtype=torch.int32, device=self.device)
@@ -819,7 +923,7 @@ class TFCLSTMEngine(_Engine):
     (mask/find_mask_kth.py:300-452, mask/gradcam.py:28-111) on libivf_hip's generic direct-convolution kernels
     (csrc/tf_clstm.hip).  Clips are NCTHW like everywhere else; `from_tf_layout` converts [B,T,H,W,C].
     The plan perturbs by freezing only and has no one-blob entry (the inherited `blob_scores` finds no symbol); `ig`,
-    `ig_path_scores`, the `rise*` entries, `smoothgrad` and `sg_noise` refuse with IvfError."""
+    `ig_path_scores`, the `rise*` and `shap*` entries, `smoothgrad` and `sg_noise` refuse with IvfError."""
     _prefix = "tfclstm"
     _has_mode = False
     _has_st = False

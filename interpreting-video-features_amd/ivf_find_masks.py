@@ -49,8 +49,16 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                     mask_mode="central", max_mask_length=None, blob_batch=32, mask_grid=None, mask_sigma=None, lam3=None,
                     max_box=None, do_intgrad=False, ig_steps=32, ig_baseline="frozen", do_rise=False, rise_masks=1024,
                     rise_p=0.5, rise_grid=None, rise_sigma=None, rise_seed=0, do_smoothgrad=False, sg_samples=32,
-                    sg_level=0.15, sg_seed=0):
-    """do_smoothgrad (the drivers' doSmoothGrad, an extension: DESIGN 15) also runs SmoothGrad, SmoothGrad^2 and VarGrad
+                    sg_level=0.15, sg_seed=0, do_shapley=False, shap_perms=64, shap_grid=None, shap_sigma=None,
+                    shap_seed=0):
+    """do_shapley (the drivers' doShapley, an extension: DESIGN 16) also runs Shapley value sampling of the target's score
+    (shap_perms permutations of the cells of shap_grid (gt, gh, gw), default (T, 1, 1): the frames; blurred by shap_sigma
+    input pixels, drawn from shap_seed; forward passes only) and writes a further list of records -- true_class,
+    pred_class, video_id, ShapHeatMap [T,H,W], ShapCells, ShapStderr [gt,gh,gw], ShapFrames [T], shap_total, n_perms, seed
+    -- to a pickle named like the Grad-CAM one with Shapley in place of GradCam; with the strips on, a further set of
+    heat-map strips (folder `shapley` beside `combined`) blends max(shap_map, 0) normalised per frame; its plan holds at
+    least blob_batch clips so that the rows of a loader batch fill it.  Off, nothing changes.
+    do_smoothgrad (the drivers' doSmoothGrad, an extension: DESIGN 15) also runs SmoothGrad, SmoothGrad^2 and VarGrad
     of the target's score (sg_samples noisy copies of each clip, noise of standard deviation sg_level * (max - min) of
     the clip drawn from sg_seed, one forward and backward each) and writes a further list of records -- true_class,
     pred_class, video_id, SGHeatMap, SGSqHeatMap, SGVarHeatMap [T,H,W], SGFrames [T], sigma, n_samples, level, seed -- to
@@ -85,6 +93,7 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
     net.eval()                                                      # smth:145
     flt = _class_filter(classOI)
     masks, time_results, cam_results, ig_results, rise_results, sg_results = [], [], [], [], [], []
+    shap_results = []
     if write_files and not os.path.exists(results_path):
         os.makedirs(results_path)
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -103,7 +112,7 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
             continue
         xs = x[keep].contiguous()
         eng = net._engine_for(xs, min_batch=blob_batch) if mask_mode in ("combi", "stcombi") or do_rise or do_smoothgrad \
-            else net._engine_for(xs)
+            or do_shapley else net._engine_for(xs)
         search = ivf_search.MaskSearch(eng, lam1, lam2, N, temporalMaskType, threshold=0.9, lr=0.2,
                                        grad_cam_type=hyper_params.get("gradCamType", "guessed"),
                                        do_gradcam=doGradCam, run_temp_mask=runTempMask,
@@ -113,10 +122,11 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                        ig_baseline=ig_baseline, do_rise=do_rise, rise_masks=rise_masks, rise_p=rise_p,
                                        rise_grid=rise_grid, rise_sigma=rise_sigma, rise_seed=rise_seed,
                                        do_smoothgrad=do_smoothgrad, sg_samples=sg_samples, sg_level=sg_level,
-                                       sg_seed=sg_seed)
+                                       sg_seed=sg_seed, do_shapley=do_shapley, shap_perms=shap_perms, shap_grid=shap_grid,
+                                       shap_sigma=shap_sigma, shap_seed=shap_seed)
         res = search.run(xs, labels[keep])
         host = {k: v.detach().cpu() for k, v in res.items()
-                if k not in ("gradcam", "box_scores", "ig_map", "rise_map", "sg_map", "sg_sq_map", "sg_var_map")}
+                if k not in ("gradcam", "box_scores", "ig_map", "rise_map", "sg_map", "sg_sq_map", "sg_var_map", "shap_map")}
         spacetime = runTempMask and mask_mode in ("spacetime", "stcombi")
         st_maps = eng.st_expand(res["st_mask"], search.st_grid(xs), mask_sigma) if spacetime and write_files and visualise \
             else None
@@ -149,6 +159,14 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                 pos = res["sg_map"].clamp_min(0.0)
                 top = pos.amax(dim=(2, 3), keepdim=True)
                 sg_heat = torch.where(top > 0, pos / torch.where(top > 0, top, torch.ones_like(top)), torch.zeros_like(pos))
+        shap_heat = None
+        if do_shapley:
+            host["shap_map"] = res["shap_map"].detach().cpu()
+            if runTempMask and write_files and visualise:
+                # as rise_heat: max(shap_map, 0) scaled to [0,1] per frame; a frame without a positive value stays all zero
+                pos = res["shap_map"].clamp_min(0.0)
+                top = pos.amax(dim=(2, 3), keepdim=True)
+                shap_heat = torch.where(top > 0, pos / torch.where(top > 0, top, torch.ones_like(top)), torch.zeros_like(pos))
         for j, bi in enumerate(keep):
             true_class = int(labels[bi])
             pred = int(host["pred_class"][j])
@@ -212,6 +230,15 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                    'SGFrames': host["sg_frames"][j].numpy().astype(np.float32),
                                    'sigma': float(host["sg_sigma"][j]), 'n_samples': int(sg_samples),
                                    'level': float(sg_level), 'seed': int(sg_seed)})
+            if do_shapley:
+                shap_results.append({'true_class': true_class, 'pred_class': pred,
+                                     'video_id': int(vid) if flavour == "smth" else vid,
+                                     'ShapHeatMap': host["shap_map"][j].numpy().astype(np.float32),
+                                     'ShapCells': host["shap_cells"][j].numpy().astype(np.float32),
+                                     'ShapStderr': host["shap_stderr"][j].numpy().astype(np.float32),
+                                     'ShapFrames': host["shap_frames"][j].numpy().astype(np.float32),
+                                     'shap_total': float(host["shap_total"][j]),
+                                     'n_perms': int(shap_perms), 'seed': int(shap_seed)})
             if runTempMask and write_files and visualise:
                 # smth:296-303 / KTH:354-367: heat-map strips with the mask dot row for both perturbation
                 # types (the dot row snaps a host copy: `tmask` keeps its sigmoid values, as the reference's
@@ -234,6 +261,10 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                         viz.create_image_arrays(xs, sg_heat[j], tmask, j, kind,
                                                 os.path.join(os.path.dirname(d), "smoothgrad"), str(vid), 0, xs.shape[4],
                                                 xs.shape[3])
+                if shap_heat is not None:
+                    for kind in ("freeze", "reverse"):
+                        viz.create_image_arrays(xs, shap_heat[j], tmask, j, kind, os.path.join(os.path.dirname(d), "shapley"),
+                                                str(vid), 0, xs.shape[4], xs.shape[3])
                 if flavour != "smth":
                     import mask as _mask
                     pert = st_pert[j] if st_pert is not None else _mask.perturb_sequence(xs, tmask, temporalMaskType)[j]
@@ -262,10 +293,14 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
         if do_smoothgrad:
             with open(os.path.join(results_path, gname.replace("GradCam", "SmoothGrad").replace(os.sep, "_")), "wb") as f:
                 pickle.dump(sg_results, f)
+        if do_shapley:
+            with open(os.path.join(results_path, gname.replace("GradCam", "Shapley").replace(os.sep, "_")), "wb") as f:
+                pickle.dump(shap_results, f)
     find_masks_impl.last_results = (time_results, cam_results)
     find_masks_impl.last_ig_results = ig_results
     find_masks_impl.last_rise_results = rise_results
     find_masks_impl.last_sg_results = sg_results
+    find_masks_impl.last_shap_results = shap_results
     return masks
 
 

@@ -244,8 +244,14 @@ class MaskSearch:
                  normalize_per_frame=True, gradcam_size=None, mask_mode="central", max_mask_length=None,
                  mask_grid=None, mask_sigma=None, lam3=None, max_box=None, do_intgrad=False, ig_steps=32,
                  ig_baseline="frozen", do_rise=False, rise_masks=1024, rise_p=0.5, rise_grid=None, rise_sigma=None,
-                 rise_seed=0, do_smoothgrad=False, sg_samples=32, sg_level=0.15, sg_seed=0):
-        """do_smoothgrad (an extension without a counterpart in the reference): also run SmoothGrad,
+                 rise_seed=0, do_smoothgrad=False, sg_samples=32, sg_level=0.15, sg_seed=0, do_shapley=False,
+                 shap_perms=64, shap_grid=None, shap_sigma=None, shap_seed=0):
+        """do_shapley (an extension without a counterpart in the reference): also run Shapley value sampling
+        of the target's score -- shap_perms permutations (every odd one the reverse of the one before) of the cells of
+        shap_grid (gt, gh, gw) (default (T, 1, 1): the frames), blurred by shap_sigma input pixels, drawn from
+        shap_seed, forward passes only; run() then also returns shap_map [b,T,H,W], shap_cells, shap_stderr, shap_count
+        [b,gt,gh,gw], shap_frames [b,T] and shap_total [b].  The perturbation is the per-pixel freeze only.
+        do_smoothgrad (an extension without a counterpart in the reference): also run SmoothGrad,
         SmoothGrad^2 and VarGrad of the target's score -- sg_samples noisy copies of each clip, noise of standard
         deviation sg_level * (max(clip) - min(clip)) drawn from sg_seed, one forward and backward each; run() then also
         returns sg_map, sg_sq_map, sg_var_map [b,T,H,W], sg_frames [b,T] and sg_sigma [b].
@@ -290,6 +296,10 @@ class MaskSearch:
             raise L.IvfError("RISE perturbs by freezing only")
         self.do_smoothgrad = bool(do_smoothgrad)                                                      # read only when on
         self.sg_samples, self.sg_level, self.sg_seed = sg_samples, sg_level, sg_seed
+        self.do_shapley = bool(do_shapley)                                                            # read only when on
+        self.shap_perms, self.shap_grid, self.shap_sigma, self.shap_seed = shap_perms, shap_grid, shap_sigma, shap_seed
+        if self.do_shapley and mask_type != "freeze":
+            raise L.IvfError("Shapley value sampling perturbs by freezing only")
 
     def run(self, x, labels, want_traj=False):
         """x [b,C,T,H,W] float32 on the GPU, labels [b] ints.  Returns a dict of device
@@ -348,6 +358,11 @@ class MaskSearch:
             r = eng.smoothgrad(x, target, n_samples=self.sg_samples, level=self.sg_level, seed=self.sg_seed)
             out["sg_map"], out["sg_sq_map"], out["sg_var_map"] = r["sg_map"], r["sq_map"], r["var_map"]
             out["sg_frames"], out["sg_sigma"] = r["sg_frames"], r["sigma"]
+        if self.do_shapley:
+            r = eng.shapley(x, target, n_perms=self.shap_perms, grid=self.shap_grid, sigma=self.shap_sigma,
+                            seed=self.shap_seed)
+            for k in ("shap_map", "shap_cells", "shap_stderr", "shap_count", "shap_frames", "shap_total"):
+                out[k] = r[k]
         return out
 
 

@@ -17,4 +17,5 @@ import ivf_search  # noqa: E402,F401
 import ivf_shard  # noqa: E402,F401
 import mask  # noqa: E402,F401
 import models  # noqa: E402,F401
+import shapley_videos  # noqa: E402,F401
 import smoothgrad_videos  # noqa: E402,F401
