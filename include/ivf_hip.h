@@ -302,6 +302,38 @@ int ivf_shap_stage(const float* x, int b, int C, int T, int H, int W, const floa
 int ivf_shap_reduce(const float* scores, const unsigned short* ranks, int b, int n, int gt, int gh, int gw, float* cells,
                     float* std_err, int* count, float* total, ivf_stream_t stream);
 
+/* ------------------------------------------------------------------ deletion / insertion curves (csrc/curve_ops.hip)
+ * An EXTENSION with no counterpart in the reference (Petsiuk et al. 2018): the faithfulness measure that
+ * compares the attribution methods.  The players are the P = gt gh gw cells of a grid as in the Shapley section above
+ * (1 <= gt <= T <= 64, 1 <= gh, gw <= 32, P <= 4096); an attribution (higher = more important) ranks them per clip, and
+ * with J = ceil(P / step), k_j = min(j step, P), j = 0 .. J:
+ *   deletion row j : cell c frozen iff rank[c] <  k_j   (row 0 the clip, row J the fully frozen clip)
+ *   insertion row j: cell c frozen iff rank[c] >= k_j   (row 0 the fully frozen clip, row J the clip)
+ * curves is a bitmask, 1 deletion, 2 insertion, 3 both (deletion first); a clip has ncurves (J+1) rows, flattened as
+ * [clip][curve][j].
+ *
+ * Rank table [b,P] (uint16) of a [b,t_in,gh,gw], t_in == gt or t_in == T (then a grid cell is the mean over the frames
+ * u of its temporal cell (u gt) / T: the fp32 sum in ascending u, one division by the frame count).  order 0:
+ *   rank[c] = #{c' : a[c'] > a[c], or a[c'] == a[c] and c' < c};       order 1 flips > to <.
+ * A NaN cell ranks after every number in either order, NaN cells among themselves by index; -0.0 == +0.0 is a tie. */
+int ivf_curve_ranks(const float* a, int b, int t_in, int T, int gt, int gh, int gw, int order, unsigned short* ranks,
+                    ivf_stream_t stream);
+/* Rows [first, first+count) of the flattened (clip, curve, j) list of b clips x [b,C,T,H,W] into p; count <= 65535.
+ * ranks [b,P] on the device: one table per clip (ivf_curve_ranks, or the caller's own).  out_cpad, A_H, A_W as
+ * ivf_shap_stage.  The rows equal (==) what ivf_stmask_expand_fwd followed by ivf_stfreeze_fwd write for the row's
+ * explicit per-frame binary S; neither S nor M is ever in memory. */
+int ivf_curve_stage(const float* x, int b, int C, int T, int H, int W, const float* A_H, const float* A_W, int gt, int gh,
+                    int gw, const unsigned short* ranks, int curves, int step, long long first, int count, float* p,
+                    int out_cpad, ivf_stream_t stream);
+/* From scores [b,ncurves,J+1] (ncurves = the curves named by the bitmask), one thread per (clip, curve), plain fp32 in
+ * ascending j, integer widths, one final division, no atomics:
+ *   auc [b,ncurves]      = (1 / (2P)) sum_{j<J} (k_{j+1} - k_j) (s_j + s_{j+1})
+ *   auc_norm [b,ncurves] = (auc - s_lo) / (s_hi - s_lo),  s_hi the score of the clip, s_lo of the fully frozen clip (the
+ *                          curve's own end rows), NaN where they are equal.
+ * Any NaN score in a curve makes both of its outputs NaN. */
+int ivf_curve_reduce(const float* scores, int b, int ncurves, int curves, int P, int step, float* auc, float* auc_norm,
+                     ivf_stream_t stream);
+
 /* ------------------------------------------------------------------ SmoothGrad, SmoothGrad^2, VarGrad (csrc/smoothgrad_ops.hip)
  * An EXTENSION with no counterpart in the reference (Smilkov et al. 2017, Hooker et al. 2019): n noisy
  * samples x + sigma z_k of a clip x [b,C,T,HW], one forward and backward each, and per input element the first two
@@ -651,6 +683,13 @@ int ivf_i3d_rise_scores(ivf_i3d_t* net, const float* x, int b, const int* target
  * allocation, no scratch beyond scores. */
 int ivf_i3d_shap_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
                         int gt, int gh, int gw, int n, const unsigned short* ranks, float* scores, ivf_stream_t stream);
+/* Scores of the deletion / insertion rows of each of b clips (extension, see ivf_curve_*): scores [b,ncurves,J+1] =
+ * probs[target[clip]] of the clip frozen per pixel by row j of each curve under the clip's own table ranks [b,P], in
+ * chunks of the plan's B rows across clip and curve boundaries (ivf_curve_stage -> forward -> pick); b may exceed B.
+ * One stream, no host synchronisation, no allocation, no scratch beyond scores. */
+int ivf_i3d_curve_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
+                         int gt, int gh, int gw, const unsigned short* ranks, int curves, int step, float* scores,
+                         ivf_stream_t stream);
 
 /* Integrated Gradients of b clips through this plan (extension, see ivf_ig_*): the b*K path points run in chunks of the
  * plan's B rows across clip boundaries (ivf_ig_stage -> forward -> backward -> ivf_ig_accumulate), then ivf_ig_finish;
@@ -771,6 +810,10 @@ int ivf_clstm_rise_scores(ivf_clstm_t* net, const float* x, int b, const int* ta
 /* ivf_i3d_shap_scores with the ConvLSTM backbone (rows staged NCTHW). */
 int ivf_clstm_shap_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
                           int gt, int gh, int gw, int n, const unsigned short* ranks, float* scores, ivf_stream_t stream);
+/* ivf_i3d_curve_scores with the ConvLSTM backbone (rows staged NCTHW). */
+int ivf_clstm_curve_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
+                           int gt, int gh, int gw, const unsigned short* ranks, int curves, int step, float* scores,
+                           ivf_stream_t stream);
 
 /* Integrated Gradients of b clips through this plan (extension, see ivf_ig_*): the b*K path points run in chunks of the
  * plan's B rows across clip boundaries (ivf_ig_stage -> forward -> backward -> ivf_ig_accumulate), then ivf_ig_finish;

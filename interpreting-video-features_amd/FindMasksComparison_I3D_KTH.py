@@ -21,7 +21,8 @@ def find_masks(dat_loader, model, config, lam1, lam2, N, ita=1, maskType="gradie
                classOI=None, verbose=True, maxMaskLength=None, doGradCam=False, runTempMask=True, maskGrid=None,
                maskSigma=None, lam3=None, maxBox=None, doIntGrad=False, igSteps=32, igBaseline="frozen", doRise=False,
                riseMasks=1024, riseProb=0.5, riseGrid=None, riseSigma=None, riseSeed=0, doSmoothGrad=False, sgSamples=32,
-               sgLevel=0.15, sgSeed=0, doShapley=False, shapPerms=64, shapGrid=None, shapSigma=None, shapSeed=0):
+               sgLevel=0.15, sgSeed=0, doShapley=False, shapPerms=64, shapGrid=None, shapSigma=None, shapSeed=0,
+               doCurves=False, curveGrid=None, curveSigma=None, curveStep=1):
     """KTH:126-380.  maskType 'combi': the exhaustive one-blob search (KTH:138-142), masks of length <=
     maxMaskLength; 'spacetime' (an extension, no counterpart in the reference): a mask per frame and cell of a
     maskGrid (gh, gw) grid, blurred by maskSigma input pixels, lam3 on the spatial TV term, records with 'st_mask';
@@ -44,7 +45,13 @@ def find_masks(dat_loader, model, config, lam1, lam2, N, ita=1, maskType="gradie
     permutations of the cells of shapGrid (gt, gh, gw) (default (T, 1, 1): the frames are the players), blurred by
     shapSigma input pixels, drawn from shapSeed, forward passes only, shapPerms (cells + 1) of them per clip -- and writes a
     further pickle of records with 'ShapHeatMap' [T,H,W], 'ShapCells' and 'ShapStderr' [gt,gh,gw], 'ShapFrames' [T],
-    'shap_total', 'n_perms', 'seed'."""
+    'shap_total', 'n_perms', 'seed'.
+    doCurves (an extension as well, whatever the maskType; freeze only) also runs the deletion and insertion curves of
+    every attribution the call produced -- the cells of curveGrid (gt, gh, gw) (default (T, 1, 1): the frames, ranked by
+    the frame profiles; with a spatial grid by the [T,H,W] maps), blurred by curveSigma input pixels, frozen or released
+    curveStep at a time in the order each attribution ranks them -- and writes a further pickle of records with 'grid',
+    'step' and per method a dict of 'ranks', 'deletion', 'insertion', 'del_auc', 'ins_auc', 'del_auc_norm',
+    'ins_auc_norm' ('random': the expected curves of a random order, when doShapley ran on the same grid)."""
     return ivf_find_masks.find_masks_impl(
         dat_loader, model, config, lam1, lam2, N, temporalMaskType, classOI, verbose, doGradCam, runTempMask,
         flavour="kth", sub_dir=_state["sub_dir"], gradcam_size=(RESIZE_SIZE_HEIGHT, RESIZE_SIZE_WIDTH),
@@ -53,7 +60,8 @@ def find_masks(dat_loader, model, config, lam1, lam2, N, ita=1, maskType="gradie
         do_intgrad=doIntGrad, ig_steps=igSteps, ig_baseline=igBaseline, do_rise=doRise, rise_masks=riseMasks,
         rise_p=riseProb, rise_grid=riseGrid, rise_sigma=riseSigma, rise_seed=riseSeed, do_smoothgrad=doSmoothGrad,
         sg_samples=sgSamples, sg_level=sgLevel, sg_seed=sgSeed, do_shapley=doShapley, shap_perms=shapPerms,
-        shap_grid=shapGrid, shap_sigma=shapSigma, shap_seed=shapSeed)
+        shap_grid=shapGrid, shap_sigma=shapSigma, shap_seed=shapSeed, do_curves=doCurves, curve_grid=curveGrid,
+        curve_sigma=curveSigma, curve_step=curveStep)
 
 
 def build_model(config, args, device):

@@ -1362,6 +1362,18 @@ extern "C" int ivf_clstm_shap_scores(ivf_clstm_t* net, const float* x, int b, co
                          (hipStream_t)stream);
 }
 
+// Deletion / insertion curves (curve_ops.hip): run_curve_scores, rows staged straight into the input buffer.
+extern "C" int ivf_clstm_curve_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H,
+                                      const float* A_W, int gt, int gh, int gw, const unsigned short* ranks, int curves,
+                                      int step, float* scores, ivf_stream_t stream) {
+  IVF_PROPAGATE(clstm_ready(net, 1));
+  IVF_CHECK_ARG(x && target && A_H && A_W && ranks && scores, "clstm_curve_scores: null pointer");
+  IVF_CHECK_ARG(b > 0, "clstm_curve_scores: bad batch %d", b);
+  IVF_CHECK_ARG(gt > 0 && gh > 0 && gw > 0, "clstm_curve_scores: bad grid (%d, %d, %d)", gt, gh, gw);
+  return run_curve_scores(backbone(net), x, b, target, A_H, A_W, gt, gh, gw, net->cfg.H, net->cfg.W, ranks, curves, step,
+                          scores, (hipStream_t)stream);
+}
+
 // Integrated Gradients (ig_ops.hip): run_ig / run_ig_path_scores on this plan; scratch from the caller.
 extern "C" int ivf_clstm_ig(ivf_clstm_t* net, const float* x, int b, const int* target, int base_kind, const float* base,
                           float base_value, const float* alpha, const float* w, int K, float* ig_map, float* frames,

@@ -232,6 +232,26 @@ static inline int run_shap_scores(const Backbone& v, const float* x, int b, cons
   });
 }
 
+// Deletion / insertion curves (curve_ops.hip; an extension): run_shap_scores with a rank table per clip --
+// per chunk ivf_curve_stage -> forward -> blob_pick on the b * ncurves * (J + 1) (clip, curve, j) rows, chunks crossing
+// clip and curve boundaries; one stream, no host synchronisation, no allocation, no scratch beyond `scores`.
+static inline int run_curve_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,
+                                   const float* A_W, int gt, int gh, int gw, int H, int W, const unsigned short* ranks,
+                                   int curves, int step, float* scores, hipStream_t s) {
+  const long long P = (long long)gt * gh * gw;
+  if (curves < 1 || curves > 3 || step < 1 || step > P || P > 4096) {     // what the row count below is made of
+    set_error("curve_scores: need curves in 1 .. 3 (got %d) and 1 <= step (%d) <= gt gh gw (%lld) <= 4096", curves, step, P);
+    return IVF_ERR_BAD_ARG;
+  }
+  const long long per = (curves == 3 ? 2 : 1) * ((P + step - 1) / step + 1);       // rows of one clip
+  return for_each_chunk(v, b * per, [&](long long first, int cnt) -> int {
+    IVF_PROPAGATE(ivf_curve_stage(x, b, v.C, v.T, H, W, A_H, A_W, gt, gh, gw, ranks, curves, step, first, cnt, v.in,
+                                  v.layout, s));
+    IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
+    return blob_pick(v.probs, target, v.K, (int)per, first, cnt, scores, s);
+  });
+}
+
 // ---------------------------------------------------------------- Integrated Gradients (ig_ops.hip)
 // An extension without a counterpart in the reference.  Its scratch belongs to the CALLER (ivf_ig_workspace_bytes), so
 // no plan's workspace size or carve order moves.

@@ -662,6 +662,152 @@ class _Engine:
         return dict(shap_scores=scores, shap_cells=cells, shap_stderr=stderr, shap_count=count, shap_total=total,
                     score_x=score_x, shap_map=self.st_expand(S, (gh, gw), sigma), shap_frames=frames * share)
 
+    # -------------------------------------------------------------- deletion / insertion curves (extension)
+    def _curve_args(self, grid, sigma, step=1, curves=3, order=0):
+        """(gt, gh, gw, step, curves, order, A_H, A_W) of a curve call, checked; grid None -> (T, 1, 1): the frames."""
+        if not self._has_st:
+            raise L.IvfError("deletion / insertion curves are built for the I3D and CLSTM plans only")
+        C, T, H, W = self.clip_shape
+        if grid is None:
+            grid = (T, 1, 1)
+        try:
+            gt, gh, gw = (int(v) for v in grid)
+        except (TypeError, ValueError):
+            raise L.IvfError(f"grid must be (gt, gh, gw), got {grid!r}")
+        if not (1 <= gt <= T <= 64 and 1 <= gh <= 32 and 1 <= gw <= 32 and gt * gh * gw <= 4096):
+            raise L.IvfError(f"grid {(gt, gh, gw)}: need 1 <= gt <= T = {T} <= 64, 1 <= gh, gw <= 32 and at most 4096 cells")
+        try:
+            step, curves = int(step), int(curves)
+        except (TypeError, ValueError):
+            raise L.IvfError(f"step and curves must be integers, got {step!r}, {curves!r}")
+        if not 1 <= step <= gt * gh * gw:
+            raise L.IvfError(f"step must be in [1, {gt * gh * gw}] cells, got {step}")
+        if curves not in (1, 2, 3):
+            raise L.IvfError(f"curves must be 1 (deletion), 2 (insertion) or 3 (both), got {curves}")
+        orders = {"morf": 0, "lerf": 1, 0: 0, 1: 1}
+        if isinstance(order, (list, dict, set)) or order not in orders:
+            raise L.IvfError(f"order must be 'morf' (most relevant first) or 'lerf', got {order!r}")
+        _, _, _, AH, AW = self._st_axes((gh, gw), sigma)
+        return gt, gh, gw, step, curves, orders[order], AH, AW
+
+    def _curve_den(self, gh, gw, sigma):
+        """The footprint weights sum_y A_H[y,i] sum_x A_W[x,j] of the pooling, fp64 on the host, stored as fp32 [gh,gw]"""
+        _, _, sigma, AH, AW = self._st_axes((gh, gw), sigma)
+        cache = self.__dict__.setdefault("_curve_den_cache", {})
+        key = (gh, gw, sigma)
+        if key not in cache:
+            den = AH.cpu().numpy().astype(np.float64).sum(axis=0)[:, None] * AW.cpu().numpy().astype(np.float64).sum(axis=0)
+            cache[key] = torch.from_numpy(den.astype(np.float32)).to(self.device)
+        return cache[key]
+
+    def curve_cells(self, attr, grid=None, sigma=None):
+        """An attribution (higher = more important) as cells [b,t_in,gh,gw], t_in = gt or T.  attr per clip: [T] (the
+        grid must then have gh = gw = 1), [gt,gh,gw], [T,gh,gw], or a pixel map [T,H,W], which is pooled per frame to
+        the footprint-weighted mean sum_yx A_H[y,i] A_W[x,j] a[u,y,x] / (sum_y A_H[y,i] sum_x A_W[x,j]): the numerator
+        by ivf_stmask_expand_bwd, the denominator fp64 on the host rounded once."""
+        gt, gh, gw, _, _, _, AH, AW = self._curve_args(grid, sigma)
+        C, T, H, W = self.clip_shape
+        L.require_gpu(attr)
+        a = L.f32c(attr)
+        shape = tuple(a.shape[1:])
+        if a.dim() == 2 and shape == (T,):
+            if gh != 1 or gw != 1:
+                raise L.IvfError(f"a frame profile [b,{T}] ranks frames only: grid {(gt, gh, gw)} needs a map")
+            return a.view(-1, T, 1, 1)
+        if a.dim() == 4 and shape in ((gt, gh, gw), (T, gh, gw)):
+            return a
+        if a.dim() == 4 and shape == (T, H, W):
+            b = a.shape[0]
+            num = torch.empty(b, T, gh, gw, device=self.device)
+            with torch.cuda.device(self.device):
+                L.check(L.lib().ivf_stmask_expand_bwd(L.ptr(a), L.ptr(AH), L.ptr(AW), L.ptr(num), b, T, gh, gw, H, W,
+                                                      L.stream()))
+            return num / self._curve_den(gh, gw, sigma)
+        raise L.IvfError(f"attribution must be [b,{T}], [b,{gt},{gh},{gw}], [b,{T},{gh},{gw}] or [b,{T},{H},{W}], "
+                         f"got {tuple(a.shape)}")
+
+    def curve_ranks(self, attr, grid=None, sigma=None, order="morf"):
+        """Per-clip rank table int16 [b, gt gh gw] (holding uint16 0 .. P-1) of an attribution (curve_cells shapes):
+        ivf_curve_ranks.  order 'morf': rank = the number of cells with a higher value, ties to the lower index;
+        'lerf' the reverse; NaN cells last either way."""
+        gt, gh, gw, _, _, order, _, _ = self._curve_args(grid, sigma, order=order)
+        cells = self.curve_cells(attr, (gt, gh, gw), sigma)
+        b, t_in = cells.shape[:2]
+        ranks = torch.empty(b, gt * gh * gw, dtype=torch.int16, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().ivf_curve_ranks(L.ptr(cells), b, t_in, self.clip_shape[1], gt, gh, gw, order, L.ptr(ranks),
+                                            L.stream()))
+        return ranks
+
+    def curve_scores(self, x, target, ranks, grid=None, sigma=None, step=1, curves=3):
+        """Scores [b, ncurves, J+1] of target[clip], J = ceil(P / step): deletion row j has the cells of rank below
+        min(j step, P) frozen per pixel, insertion row j the others; ranks [b,P] is each clip's own table.
+        ivf_*_curve_scores, forward only, chunks of the plan's max_batch rows across clips and curves; b may exceed
+        max_batch."""
+        gt, gh, gw, step, curves, _, AH, AW = self._curve_args(grid, sigma, step, curves)
+        x = self._clip(x, any_batch=True)
+        b, P = x.shape[0], gt * gh * gw
+        tgt = self._targets(target, b)
+        L.require_gpu(ranks)
+        if ranks.dtype != torch.int16 or tuple(ranks.shape) != (b, P):
+            raise L.IvfError(f"ranks must be an int16 [{b},{P}] tensor, got {ranks.dtype} {tuple(ranks.shape)}")
+        ranks = ranks.contiguous()
+        scores = torch.empty(b, 2 if curves == 3 else 1, -(-P // step) + 1, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(self._fn("curve_scores")(self._h, L.ptr(x), b, L.ptr(tgt), L.ptr(AH), L.ptr(AW), gt, gh, gw,
+                                             L.ptr(ranks), curves, step, L.ptr(scores), L.stream()))
+        return scores
+
+    def curve_reduce(self, scores, grid=None, step=1, curves=3):
+        """ivf_curve_reduce on scores [b,ncurves,J+1]: (auc, auc_norm) [b,ncurves]; the trapezoid over the fraction of
+        cells, and it rescaled so that the fully frozen clip is 0 and the clip 1 (NaN where the two scores are equal)."""
+        gt, gh, gw, step, curves, _, _, _ = self._curve_args(grid, 0.0, step, curves)
+        s = L.f32c(scores)
+        L.require_gpu(s)
+        P = gt * gh * gw
+        want = (2 if curves == 3 else 1, -(-P // step) + 1)
+        if s.dim() != 3 or tuple(s.shape[1:]) != want:
+            raise L.IvfError(f"scores must be [b,{want[0]},{want[1]}] for grid {(gt, gh, gw)}, step {step}, curves "
+                             f"{curves}; got {tuple(s.shape)}")
+        b = s.shape[0]
+        auc, norm = torch.empty(b, want[0], device=s.device), torch.empty(b, want[0], device=s.device)
+        with torch.cuda.device(s.device):
+            L.check(L.lib().ivf_curve_reduce(L.ptr(s), b, want[0], curves, P, step, L.ptr(auc), L.ptr(norm), L.stream()))
+        return auc, norm
+
+    def curve_random_baseline(self, shap_scores):
+        """The expected curves of a random ranking from Shapley rows [b,n,P+1] of the same grid and sigma: [b,2,P+1] =
+        (mean_k s[k][j], mean_k s[k][P-j]), deletion then insertion, ready for curve_reduce at step 1."""
+        if not self._has_st:
+            raise L.IvfError("deletion / insertion curves are built for the I3D and CLSTM plans only")
+        s = L.f32c(shap_scores)
+        if s.dim() != 3:
+            raise L.IvfError(f"shap_scores must be [b, n_perms, P+1], got {tuple(s.shape)}")
+        m = s.mean(dim=1)
+        return torch.stack([m, m.flip(-1)], dim=1).contiguous()
+
+    def faithfulness(self, x, target, attr, grid=None, sigma=None, step=1, order="morf"):
+        """Deletion and insertion curves (Petsiuk et al. 2018) of an attribution for target[clip] on b clips, b may
+        exceed max_batch: the cells of grid = (gt, gh, gw) (default (T, 1, 1): the frames) are frozen per pixel
+        (deletion) or released from the fully frozen clip (insertion) in the order the attribution ranks them, `step`
+        cells per forward.  Returns a dict of device tensors: curve_ranks int16 [b,P], del_scores, ins_scores [b,J+1],
+        del_auc, ins_auc, del_auc_norm, ins_auc_norm [b], score_x [b] (the plan's ordinary forward).  A faithful
+        attribution under 'morf' has a low deletion and a high insertion AUC."""
+        gt, gh, gw, step, _, order, _, _ = self._curve_args(grid, sigma, step, 3, order)
+        x = self._clip(x, any_batch=True)
+        b = x.shape[0]
+        tgt = self._targets(target, b)
+        idx = tgt.long().view(-1, 1)
+        score_x = torch.cat([self.forward(x[i:i + self.max_batch]).gather(1, idx[i:i + self.max_batch])
+                             for i in range(0, b, self.max_batch)])[:, 0].contiguous()
+        ranks = self.curve_ranks(attr, (gt, gh, gw), sigma, order)
+        if ranks.shape[0] != b:
+            raise L.IvfError(f"need an attribution for each of the {b} clips, got {ranks.shape[0]}")
+        scores = self.curve_scores(x, tgt, ranks, (gt, gh, gw), sigma, step, 3)
+        auc, norm = self.curve_reduce(scores, (gt, gh, gw), step, 3)
+        return dict(curve_ranks=ranks, del_scores=scores[:, 0], ins_scores=scores[:, 1], del_auc=auc[:, 0],
+                    ins_auc=auc[:, 1], del_auc_norm=norm[:, 0], ins_auc_norm=norm[:, 1], score_x=score_x)
+
     def argmax(self, probs):
         b = probs.shape[0]
         t = torch.empty(b, dtype=torch.int32, device=self.device)
@@ -923,7 +1069,8 @@ class TFCLSTMEngine(_Engine):
     (mask/find_mask_kth.py:300-452, mask/gradcam.py:28-111) on libivf_hip's generic direct-convolution kernels
     (csrc/tf_clstm.hip).  Clips are NCTHW like everywhere else; `from_tf_layout` converts [B,T,H,W,C].
     The plan perturbs by freezing only and has no one-blob entry (the inherited `blob_scores` finds no symbol); `ig`,
-    `ig_path_scores`, the `rise*` and `shap*` entries, `smoothgrad` and `sg_noise` refuse with IvfError."""
+    `ig_path_scores`, the `rise*`, `shap*` and `curve*` entries, `faithfulness`, `smoothgrad` and `sg_noise` refuse with
+    IvfError."""
     _prefix = "tfclstm"
     _has_mode = False
     _has_st = False

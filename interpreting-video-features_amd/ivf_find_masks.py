@@ -50,8 +50,17 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                     max_box=None, do_intgrad=False, ig_steps=32, ig_baseline="frozen", do_rise=False, rise_masks=1024,
                     rise_p=0.5, rise_grid=None, rise_sigma=None, rise_seed=0, do_smoothgrad=False, sg_samples=32,
                     sg_level=0.15, sg_seed=0, do_shapley=False, shap_perms=64, shap_grid=None, shap_sigma=None,
-                    shap_seed=0):
-    """do_shapley (the drivers' doShapley, an extension: DESIGN 16) also runs Shapley value sampling of the target's score
+                    shap_seed=0, do_curves=False, curve_grid=None, curve_sigma=None, curve_step=1):
+    """do_curves (the drivers' doCurves, an extension: DESIGN 17) also runs the deletion and insertion curves of every
+    attribution the call produced (ivf_search.MaskSearch: the frame profiles on the default frame grid, the [T,H,W] maps
+    on a spatial curve_grid; curve_sigma the blur in input pixels, curve_step cells per forward; freeze only) and writes
+    a further list of records -- true_class, pred_class, video_id, grid, step, and per method ('time_mask' or
+    'st_mask', 'gradcam', 'ig', 'rise', 'sg', 'shap', and 'random' when Shapley ran on the same grid and sigma) a dict
+    of ranks [P] (None for 'random'), deletion, insertion [J+1], del_auc, ins_auc, del_auc_norm, ins_auc_norm -- to a
+    pickle named like the Grad-CAM one with Curves in place of GradCam; its plan holds at least blob_batch clips so that
+    the rows of a loader batch fill it.  The multi-GPU record gather (ivf_shard) does not carry these records.  Off,
+    nothing changes.
+    do_shapley (the drivers' doShapley, an extension: DESIGN 16) also runs Shapley value sampling of the target's score
     (shap_perms permutations of the cells of shap_grid (gt, gh, gw), default (T, 1, 1): the frames; blurred by shap_sigma
     input pixels, drawn from shap_seed; forward passes only) and writes a further list of records -- true_class,
     pred_class, video_id, ShapHeatMap [T,H,W], ShapCells, ShapStderr [gt,gh,gw], ShapFrames [T], shap_total, n_perms, seed
@@ -93,7 +102,7 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
     net.eval()                                                      # smth:145
     flt = _class_filter(classOI)
     masks, time_results, cam_results, ig_results, rise_results, sg_results = [], [], [], [], [], []
-    shap_results = []
+    shap_results, curve_results = [], []
     if write_files and not os.path.exists(results_path):
         os.makedirs(results_path)
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -112,7 +121,7 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
             continue
         xs = x[keep].contiguous()
         eng = net._engine_for(xs, min_batch=blob_batch) if mask_mode in ("combi", "stcombi") or do_rise or do_smoothgrad \
-            or do_shapley else net._engine_for(xs)
+            or do_shapley or do_curves else net._engine_for(xs)
         search = ivf_search.MaskSearch(eng, lam1, lam2, N, temporalMaskType, threshold=0.9, lr=0.2,
                                        grad_cam_type=hyper_params.get("gradCamType", "guessed"),
                                        do_gradcam=doGradCam, run_temp_mask=runTempMask,
@@ -123,7 +132,8 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                        rise_grid=rise_grid, rise_sigma=rise_sigma, rise_seed=rise_seed,
                                        do_smoothgrad=do_smoothgrad, sg_samples=sg_samples, sg_level=sg_level,
                                        sg_seed=sg_seed, do_shapley=do_shapley, shap_perms=shap_perms, shap_grid=shap_grid,
-                                       shap_sigma=shap_sigma, shap_seed=shap_seed)
+                                       shap_sigma=shap_sigma, shap_seed=shap_seed, do_curves=do_curves,
+                                       curve_grid=curve_grid, curve_sigma=curve_sigma, curve_step=curve_step)
         res = search.run(xs, labels[keep])
         host = {k: v.detach().cpu() for k, v in res.items()
                 if k not in ("gradcam", "box_scores", "ig_map", "rise_map", "sg_map", "sg_sq_map", "sg_var_map", "shap_map")}
@@ -239,6 +249,21 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                      'ShapFrames': host["shap_frames"][j].numpy().astype(np.float32),
                                      'shap_total': float(host["shap_total"][j]),
                                      'n_perms': int(shap_perms), 'seed': int(shap_seed)})
+            if do_curves:
+                T_ = xs.shape[2]
+                rec = {'true_class': true_class, 'pred_class': pred, 'video_id': int(vid) if flavour == "smth" else vid,
+                       'grid': (T_, 1, 1) if curve_grid is None else tuple(int(v) for v in curve_grid),
+                       'step': int(curve_step)}
+                for key in host:
+                    if key.startswith("curves_") and key.endswith("_deletion"):
+                        m = key[len("curves_"):-len("_deletion")]
+                        rk = host.get(f"curves_{m}_ranks")
+                        rec[m] = {'ranks': None if rk is None else rk[j].numpy().astype(np.int64) & 0xFFFF,
+                                  'deletion': host[key][j].numpy().astype(np.float32),
+                                  'insertion': host[f"curves_{m}_insertion"][j].numpy().astype(np.float32)}
+                        for k in ("del_auc", "ins_auc", "del_auc_norm", "ins_auc_norm"):
+                            rec[m][k] = float(host[f"curves_{m}_{k}"][j])
+                curve_results.append(rec)
             if runTempMask and write_files and visualise:
                 # smth:296-303 / KTH:354-367: heat-map strips with the mask dot row for both perturbation
                 # types (the dot row snaps a host copy: `tmask` keeps its sigmoid values, as the reference's
@@ -296,11 +321,15 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
         if do_shapley:
             with open(os.path.join(results_path, gname.replace("GradCam", "Shapley").replace(os.sep, "_")), "wb") as f:
                 pickle.dump(shap_results, f)
+        if do_curves:
+            with open(os.path.join(results_path, gname.replace("GradCam", "Curves").replace(os.sep, "_")), "wb") as f:
+                pickle.dump(curve_results, f)
     find_masks_impl.last_results = (time_results, cam_results)
     find_masks_impl.last_ig_results = ig_results
     find_masks_impl.last_rise_results = rise_results
     find_masks_impl.last_sg_results = sg_results
     find_masks_impl.last_shap_results = shap_results
+    find_masks_impl.last_curve_results = curve_results
     return masks
 
 

@@ -109,6 +109,10 @@ _SIGS = {
     "ivf_shap_ranks": (c_int, [_U] + [_I] * 6 + [_P, _P]),
     "ivf_shap_stage": (c_int, [_P] + [_I] * 5 + [_P, _P] + [_I] * 4 + [_P, ctypes.c_longlong, _I, _P, _I, _P]),
     "ivf_shap_reduce": (c_int, [_P, _P] + [_I] * 5 + [_P] * 5),
+    # csrc/curve_ops.hip (deletion / insertion curves, documented extension)
+    "ivf_curve_ranks": (c_int, [_P] + [_I] * 7 + [_P, _P]),
+    "ivf_curve_stage": (c_int, [_P] + [_I] * 5 + [_P, _P] + [_I] * 3 + [_P, _I, _I, ctypes.c_longlong, _I, _P, _I, _P]),
+    "ivf_curve_reduce": (c_int, [_P] + [_I] * 5 + [_P] * 3),
     # csrc/ig_ops.hip (Integrated Gradients, documented extension)
     "ivf_ig_stage": (c_int, [_P, _I, _P, _F, _P] + [_I] * 5 + [ctypes.c_longlong, _I, _P, _I, _P]),
     "ivf_ig_accumulate": (c_int, [_P, _I, _P, _I, ctypes.c_longlong, _I, _P] + [_I] * 4 + [_P]),
@@ -167,6 +171,7 @@ _SIGS = {
     "ivf_i3d_box_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 5 + [_P, _P]),
     "ivf_i3d_rise_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_U, _U, _P, _P]),
     "ivf_i3d_shap_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_P, _P, _P]),
+    "ivf_i3d_curve_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 3 + [_P, _I, _I, _P, _P]),
     "ivf_i3d_smoothgrad": (c_int, [_P, _P, _I, _P, _I, _F, _U] + [_P] * 10),
     "ivf_i3d_gradcam": (c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "ivf_i3d_gradcam_layer": (c_int, [_P, _P, _I, _P, c_char_p, _I, _I, _I, _P, _P, _P]),
@@ -208,6 +213,7 @@ _SIGS = {
     "ivf_clstm_box_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 5 + [_P, _P]),
     "ivf_clstm_rise_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_U, _U, _P, _P]),
     "ivf_clstm_shap_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_P, _P, _P]),
+    "ivf_clstm_curve_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 3 + [_P, _I, _I, _P, _P]),
     "ivf_clstm_smoothgrad": (c_int, [_P, _P, _I, _P, _I, _F, _U] + [_P] * 10),
     "ivf_clstm_gradcam_reduce": (c_int, [_P, _P, POINTER(c_int), _I, _P, _P, _I, _I, _I, _I, _P]),
     "ivf_clstm_set_cam_steps": (c_int, [_P, POINTER(c_int), _I]),

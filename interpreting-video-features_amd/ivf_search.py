@@ -245,8 +245,19 @@ class MaskSearch:
                  mask_grid=None, mask_sigma=None, lam3=None, max_box=None, do_intgrad=False, ig_steps=32,
                  ig_baseline="frozen", do_rise=False, rise_masks=1024, rise_p=0.5, rise_grid=None, rise_sigma=None,
                  rise_seed=0, do_smoothgrad=False, sg_samples=32, sg_level=0.15, sg_seed=0, do_shapley=False,
-                 shap_perms=64, shap_grid=None, shap_sigma=None, shap_seed=0):
-        """do_shapley (an extension without a counterpart in the reference): also run Shapley value sampling
+                 shap_perms=64, shap_grid=None, shap_sigma=None, shap_seed=0, do_curves=False, curve_grid=None,
+                 curve_sigma=None, curve_step=1):
+        """do_curves (an extension without a counterpart in the reference): also run the deletion and
+        insertion curves (Petsiuk et al. 2018) of every attribution this call produced, on the cells of curve_grid
+        (gt, gh, gw) (default (T, 1, 1): the frames), blurred by curve_sigma input pixels, curve_step cells per forward.
+        With a frame grid (gh = gw = 1) the attributions are the frame profiles -- time_mask (named 'st_mask' where it
+        is the frame means of st_mask), the per-frame mean of the Grad-CAM map, ig_frames, rise_frames, sg_frames,
+        shap_frames; with a spatial grid they are the [T,H,W] maps (the expanded st_mask, gradcam, ig_map, rise_map,
+        sg_map, shap_map) and a method without one is left out.  'random' (the expected curves of a random order, at
+        step 1) is added when Shapley ran on the same grid and sigma.  run() then also returns, per method m,
+        curves_<m>_ranks [b,P] (not for 'random'), curves_<m>_deletion, curves_<m>_insertion [b,J+1],
+        curves_<m>_del_auc, _ins_auc, _del_auc_norm, _ins_auc_norm [b].  The perturbation is the per-pixel freeze only.
+        do_shapley (an extension without a counterpart in the reference): also run Shapley value sampling
         of the target's score -- shap_perms permutations (every odd one the reverse of the one before) of the cells of
         shap_grid (gt, gh, gw) (default (T, 1, 1): the frames), blurred by shap_sigma input pixels, drawn from
         shap_seed, forward passes only; run() then also returns shap_map [b,T,H,W], shap_cells, shap_stderr, shap_count
@@ -300,6 +311,10 @@ class MaskSearch:
         self.shap_perms, self.shap_grid, self.shap_sigma, self.shap_seed = shap_perms, shap_grid, shap_sigma, shap_seed
         if self.do_shapley and mask_type != "freeze":
             raise L.IvfError("Shapley value sampling perturbs by freezing only")
+        self.do_curves = bool(do_curves)                                                              # read only when on
+        self.curve_grid, self.curve_sigma, self.curve_step = curve_grid, curve_sigma, curve_step
+        if self.do_curves and mask_type != "freeze":
+            raise L.IvfError("deletion / insertion curves perturb by freezing only")
 
     def run(self, x, labels, want_traj=False):
         """x [b,C,T,H,W] float32 on the GPU, labels [b] ints.  Returns a dict of device
@@ -363,7 +378,55 @@ class MaskSearch:
                             seed=self.shap_seed)
             for k in ("shap_map", "shap_cells", "shap_stderr", "shap_count", "shap_frames", "shap_total"):
                 out[k] = r[k]
+        if self.do_curves:
+            self._run_curves(x, target, out, r["shap_scores"] if self.do_shapley else None)
         return out
+
+    def _curve_attributions(self, x, out, spatial):
+        """{method: attribution} of what this call produced: frame profiles [b,T], or on a spatial grid [b,T,H,W] maps"""
+        T, HW = x.shape[2], tuple(x.shape[3:])
+        attrs = {}
+        if spatial:
+            if "st_mask" in out:
+                attrs["st_mask"] = self.engine.st_expand(out["st_mask"], self.st_grid(x), self.mask_sigma)
+            for name, key in (("gradcam", "gradcam"), ("ig", "ig_map"), ("rise", "rise_map"), ("sg", "sg_map"),
+                              ("shap", "shap_map")):
+                if key in out and tuple(out[key].shape[1:]) == (T,) + HW:
+                    attrs[name] = out[key]
+            return attrs
+        if "time_mask" in out:
+            attrs["st_mask" if "st_mask" in out else "time_mask"] = out["time_mask"]
+        if "gradcam" in out and out["gradcam"].shape[1] == T:
+            attrs["gradcam"] = out["gradcam"].float().mean(dim=(2, 3))
+        for name, key in (("ig", "ig_frames"), ("rise", "rise_frames"), ("sg", "sg_frames"), ("shap", "shap_frames")):
+            if key in out:
+                attrs[name] = out[key]
+        return attrs
+
+    def _run_curves(self, x, target, out, shap_scores):
+        eng = self.engine
+        T, H = x.shape[2], x.shape[3]
+        grid = (T, 1, 1) if self.curve_grid is None else tuple(int(v) for v in self.curve_grid)
+        if len(grid) != 3:
+            raise L.IvfError(f"curve_grid must be (gt, gh, gw), got {self.curve_grid!r}")
+        names = ("del_auc", "ins_auc", "del_auc_norm", "ins_auc_norm")
+        for m, attr in self._curve_attributions(x, out, grid[1] > 1 or grid[2] > 1).items():
+            r = eng.faithfulness(x, target, attr, grid=grid, sigma=self.curve_sigma, step=self.curve_step)
+            out[f"curves_{m}_ranks"] = r["curve_ranks"]
+            out[f"curves_{m}_deletion"], out[f"curves_{m}_insertion"] = r["del_scores"], r["ins_scores"]
+            for k in names:
+                out[f"curves_{m}_{k}"] = r[k]
+        if shap_scores is not None:
+            sgrid = (T, 1, 1) if self.shap_grid is None else tuple(int(v) for v in self.shap_grid)
+
+            def blur(sigma, g):
+                return 0.5 * H / g[1] if sigma is None else float(sigma)
+            if sgrid == grid and blur(self.shap_sigma, sgrid) == blur(self.curve_sigma, grid):
+                s = eng.curve_random_baseline(shap_scores)
+                auc, norm = eng.curve_reduce(s, grid, 1, 3)
+                out["curves_random_deletion"], out["curves_random_insertion"] = s[:, 0], s[:, 1]
+                out["curves_random_del_auc"], out["curves_random_ins_auc"] = auc[:, 0], auc[:, 1]
+                out["curves_random_del_auc_norm"], out["curves_random_ins_auc_norm"] = norm[:, 0], norm[:, 1]
 
 
     def _run_combi(self, x, target, probs, out):

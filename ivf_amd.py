@@ -8,6 +8,7 @@ _PKG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "interpreting-vi
 if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
+import faithfulness_videos  # noqa: E402,F401
 import grad_cam_videos  # noqa: E402,F401
 import ivf_engine  # noqa: E402,F401
 import ivf_find_masks  # noqa: E402,F401
