@@ -91,6 +91,13 @@ struct ivf_i3d {
   std::vector<Op> ops;
   int feat_buf = -1;
   int cam_buf = -1;      // Grad-CAM target endpoint of the pass in flight (-1: none): its gradient stays UNGATED
+  // bf16 storage with the stem at temporal stride 1: the stem's backward is a depth-to-space conv with an fp32 output,
+  // which only the LDS-halo kernel writes from bf16 gradients, and that kernel has no 7-tap form.  The plan then widens
+  // grad(stem output) to fp32 once (off_stem_dy32) and runs that one conv in the 3-pass split on weights packed for it:
+  // bf16-valued operands have no low plane, so the sum is the two plane products of the bf16act form.
+  bool stem_bwd_wide = false;
+  size_t off_stem_dy32 = 0;
+  int bwd_math(int conv) const { return (stem_bwd_wide && conv == 0) ? (int)IVF_MATH_BF16X3 : (int)cfg.math; }
   size_t weights_floats = 0;
   size_t ws_bytes = 0;
   // misc workspace offsets (bytes)
@@ -300,6 +307,7 @@ static int build_plan(ivf_i3d* n) {
     }
   }
 
+  n->stem_bwd_wide = n->act16() && c.stem_stride_t == 1;
   // ---- weights arena layout (floats)
   size_t w = 0;
   auto take = [&](size_t elems) { size_t o = w; w += (elems + 63) / 64 * 64; return o; };
@@ -316,7 +324,7 @@ static int build_plan(ivf_i3d* n) {
     L.wf_elems = ivf_conv3d_pack_fwd_elems(L.cout, L.cinp, L.k[0], L.k[1], L.k[2], c.math);
     L.wf_off = take(L.wf_elems);
     L.wb_elems = ivf_conv3d_pack_bwd_elems(L.cout, L.cinp, L.k[0], L.k[1], L.k[2], L.s[0], L.s[1], L.s[2],
-                                           L.pad[0], L.pad[1], L.pad[2], c.math);
+                                           L.pad[0], L.pad[1], L.pad[2], n->bwd_math((int)i));
     L.wb_off = take(L.wb_elems);
     L.scale_off = take(L.cout);
     L.shift_off = take(L.cout);
@@ -379,6 +387,7 @@ static int build_plan(ivf_i3d* n) {
   n->off_camw = takeb(B * 1024 * 4);
   n->off_mm = takeb(B * max_t * 2 * 4);
   n->off_dfeat_raw = takeb(B * f.per_clip() * 4);
+  if (n->stem_bwd_wide) n->off_stem_dy32 = takeb(B * n->bufs[n->ops[0].dst].per_clip() * 4);
   n->sc.carve_pairs(takeb, B, T, 12);
   n->ws_bytes = bytes;
   n->loaded.assign(n->convs.size(), false);
@@ -423,7 +432,7 @@ static void fill_conv_bwd(const ivf_i3d* n, const Op& o, int b, ivf_conv3d_desc*
   d->out_ld = s.C; d->out_coff = o.src_coff;
   d->accumulate = o.bwd_accumulate;
   d->mask_ld = s.C; d->mask_coff = o.src_coff;
-  d->math = n->cfg.math;
+  d->math = n->bwd_math(o.conv);
   if (o.bwd_fused) {
     // one GEMM over [dY_b0 | dT_b1a | dT_b2a] -> d(input of the module)
     const ActBuf& t12 = n->bufs[o.src2];
@@ -463,6 +472,12 @@ static void fill_pool(const ivf_i3d* n, const Op& o, int b, ivf_pool3d_desc* d) 
   d->act_bf16 = n->act16();
 }
 
+// bf16 -> fp32, element for element (see ivf_i3d::stem_bwd_wide)
+__global__ void widen_bf16_kernel(const unsigned short* __restrict__ in, float* __restrict__ out, size_t n) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    out[i] = __uint_as_float((unsigned)in[i] << 16);
+}
+
 // One convolution site -- an op in one direction (0 forward, 1 backward-data) -- on b clips with kernel variant
 // `variant`.  Forward reads the unit's own pack or the fused [b0 | b1a | b2a] group's; backward the unit's own or the
 // fused 1x1x1 GEMM's, and gates the gradient it writes through the 1-bit record where the plan keeps one, else through
@@ -489,7 +504,15 @@ static int launch_conv_site(const ivf_i3d* n, const Op& o, int dir, int b, int v
     gate = nullptr;
   }
   prof_set_flops((o.bwd_fused ? o.flops_bwd_per_clip : o.flops_per_clip) * b);
-  return ivf_conv3d(&d, n->grad(o.dst), W + (o.bwd_fused ? L.fus_wb_off : L.wb_off), nullptr, nullptr, gate, n->grad(o.src), s);
+  const float* dy = n->grad(o.dst);
+  if (n->stem_bwd_wide && o.conv == 0) {
+    float* wide = n->at<float>(n->off_stem_dy32);
+    const size_t cnt = (size_t)b * n->bufs[o.dst].per_clip();
+    hipLaunchKernelGGL(widen_bf16_kernel, dim3(grid_for(cnt)), dim3(256), 0, s, (const unsigned short*)dy, wide, cnt);
+    IVF_CHECK_LAUNCH();
+    dy = wide;
+  }
+  return ivf_conv3d(&d, dy, W + (o.bwd_fused ? L.fus_wb_off : L.wb_off), nullptr, nullptr, gate, n->grad(o.src), s);
 }
 
 static int check_ready(const ivf_i3d* n, int b) {
@@ -752,7 +775,7 @@ extern "C" int ivf_i3d_load_conv(ivf_i3d_t* net, int i, const float* w, const fl
   IVF_PROPAGATE(ivf_conv3d_pack_fwd(w, A + L.wf_off, L.cout, L.cin, L.cinp, L.k[0], L.k[1], L.k[2],
                                     net->cfg.math, s));
   IVF_PROPAGATE(ivf_conv3d_pack_bwd(w, A + L.scale_off, A + L.wb_off, L.cout, L.cin, L.cinp, L.k[0], L.k[1],
-                                    L.k[2], L.s[0], L.s[1], L.s[2], L.pad[0], L.pad[1], L.pad[2], net->cfg.math,
+                                    L.k[2], L.s[0], L.s[1], L.s[2], L.pad[0], L.pad[1], L.pad[2], net->bwd_math(i),
                                     &L.geom, s));
   if (L.grp_owner >= 0) {
     const ConvLayer& G = net->convs[L.grp_owner];

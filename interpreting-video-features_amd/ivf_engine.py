@@ -916,6 +916,8 @@ class I3DEngine(_Engine):
         off = p.value - self._ws.data_ptr()
         n = b * T.value * H.value * W.value * ld.value
         esz = L.lib().ivf_i3d_act_elem_bytes(self._h)           # 2: bf16 storage (math="bf16act")
+        if name.split(":")[0] == "input":
+            esz = 4                                             # the clip and its gradient stay fp32 in every mode
         flat = self._ws[off:off + esz * n].view(torch.float32 if esz == 4 else torch.bfloat16).float()
         return flat.view(b, T.value, H.value, W.value, ld.value)[..., :C.value].permute(0, 4, 1, 2, 3).contiguous()
 

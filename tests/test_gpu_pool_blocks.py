@@ -33,13 +33,14 @@ def geometry(thw, k, s):
     return pads, outs
 
 
-def pool_fwd_ref(x, k, s, pads, outs, dead):
-    """x [B,T,H,W,C] fp32 -> (y [B,To,Ho,Wo,C] fp32, code [B,To,Ho,Wo,C] uint8)"""
+def pool_fwd_ref(x, k, s, pads, outs, dead, dtype=np.float32):
+    """x [B,T,H,W,C] fp32 -> (y [B,To,Ho,Wo,C] fp32, code [B,To,Ho,Wo,C] uint8); dtype: the arithmetic of the rule
+    (float64: the same rule on an fp64 network, tests/i3d_refs.py)"""
     Bn, T, H, W, Cn = x.shape
     ext = [(o - 1) * ss + kk for o, ss, kk in zip(outs, s, k)]
-    xp = np.zeros((Bn, max(ext[0], pads[0] + T), max(ext[1], pads[1] + H), max(ext[2], pads[2] + W), Cn), np.float32)
+    xp = np.zeros((Bn, max(ext[0], pads[0] + T), max(ext[1], pads[1] + H), max(ext[2], pads[2] + W), Cn), dtype)
     xp[:, pads[0]:pads[0] + T, pads[1]:pads[1] + H, pads[2]:pads[2] + W] = x
-    y = np.zeros((Bn,) + tuple(outs) + (Cn,), np.float32)
+    y = np.zeros((Bn,) + tuple(outs) + (Cn,), dtype)
     code = np.zeros(y.shape, np.uint8)
     for to, ho, wo in itertools.product(*map(range, outs)):
         best = bi = None
@@ -59,10 +60,10 @@ def pool_fwd_ref(x, k, s, pads, outs, dead):
     return y, code
 
 
-def pool_bwd_ref(dy, code, x_shape, k, s, pads, old, gate):
+def pool_bwd_ref(dy, code, x_shape, k, s, pads, old, gate, dtype=np.float32):
     """dy, code [B,To,Ho,Wo,C]; old: dX to accumulate into or None; gate: the relu_mask tensor or None"""
     Bn, T, H, W, Cn = x_shape
-    dx = np.zeros(x_shape, np.float32) if old is None else old.astype(np.float32).copy()
+    dx = np.zeros(x_shape, dtype) if old is None else old.astype(dtype).copy()
     bb, cc = np.meshgrid(np.arange(Bn), np.arange(Cn), indexing='ij')
     _, To, Ho, Wo, _ = dy.shape
     for to, ho, wo in itertools.product(range(To), range(Ho), range(Wo)):
@@ -74,7 +75,7 @@ def pool_bwd_ref(dy, code, x_shape, k, s, pads, old, gate):
         dx[bb[ok], ti[ok], hi[ok], wi[ok], cc[ok]] += dy[:, to, ho, wo][ok]
     if gate is not None:
         with np.errstate(invalid='ignore'):
-            dx = np.where(gate > 0, dx, np.float32(0))
+            dx = np.where(gate > 0, dx, dtype(0))
     return dx
 
 
