@@ -561,6 +561,32 @@ int ivf_gradcam_reduce(const float* feat, const float* grad, float* weights, flo
 int ivf_gradcam_reduce_bf16(const void* feat, const void* grad, float* weights, float* cam, int B, int npos,
                             int C, ivf_stream_t stream);
 
+/* The activation-map family around Grad-CAM (csrc/cam_ops.hip; a documented extension), from the same
+ * two buffers: feat = A and grad = G, [B,npos,C] channels-last.  Per clip, s_k = sum_p A[p,k]:
+ *   IVF_CAM_GRADCAM  w_k = mean_p G                                  cam[p] = relu(sum_k w_k A[p,k])
+ *   IVF_CAM_PP       w_k = sum_p [G > 0] G / (2 + s_k G)             cam[p] = relu(sum_k w_k A[p,k])   (Grad-CAM++)
+ *   IVF_CAM_XGRAD    w_k = (sum_p G A) / s_k, 0 where s_k == 0       cam[p] = relu(sum_k w_k A[p,k])   (XGrad-CAM)
+ *   IVF_CAM_HIRES    w_k = 0 (none)                                  cam[p] = relu(sum_k G[p,k] A[p,k])
+ *   IVF_CAM_LAYER    w_k = 0 (none)                                  cam[p] = relu(sum_k relu(G[p,k]) A[p,k])
+ * kinds_host: n_kinds (1..5) distinct HOST ints; row i of weights [n_kinds,B,C] (optional) and of cam
+ * [n_kinds,B,npos] belongs to kinds_host[i].  Kind 0 runs the kernels of ivf_gradcam_reduce (bit-equal to it).
+ * No atomics, fixed summation order: a clip's rows depend neither on B, nor on its place in the batch, nor on the
+ * other kinds of the call.  Non-finite values propagate as in Grad-CAM; the one guard is XGrad-CAM's s_k == 0.
+ * The per-channel passes run over chunks of IVF_CAM_CHUNK positions; ws: ivf_cam_ws_bytes(B, npos, C) bytes. */
+#define IVF_CAM_GRADCAM 0
+#define IVF_CAM_PP 1
+#define IVF_CAM_XGRAD 2
+#define IVF_CAM_HIRES 3
+#define IVF_CAM_LAYER 4
+#define IVF_CAM_CHUNK 128
+#define IVF_CAM_MAX_HID 256
+size_t ivf_cam_ws_bytes(int B, int npos, int C);
+int ivf_cam_reduce(const float* feat, const float* grad, int n_kinds, const int* kinds_host, float* weights,
+                   float* cam, void* ws, int B, int npos, int C, ivf_stream_t stream);
+/* feat and grad stored as bf16 (IVF_MATH_BF16ACT plans); weights and cam fp32. */
+int ivf_cam_reduce_bf16(const void* feat, const void* grad, int n_kinds, const int* kinds_host, float* weights,
+                        float* cam, void* ws, int B, int npos, int C, ivf_stream_t stream);
+
 /* grad_cam_videos.py:113-138: per temporal slice bilinear resize (sh,sw)->(H,W)
  * (OpenCV INTER_LINEAR rule), repeat `step` frames, min/max normalise per slice block
  * (per_frame) or per clip.  cam [B,nslice,sh,sw] -> out [B,nslice*step,H,W];
@@ -727,6 +753,17 @@ int ivf_i3d_gradcam(ivf_i3d_t* net, const float* x, int b, const int* target, in
  * Grad-CAM reduction on [T',H',W',C'] and the resize with step = T / T'. */
 int ivf_i3d_gradcam_layer(ivf_i3d_t* net, const float* x, int b, const int* target, const char* layer,
                           int per_frame, int out_h, int out_w, float* cam, float* probs, ivf_stream_t stream);
+/* The Grad-CAM family on one endpoint (a documented extension): ONE forward and ONE backward down to `layer` as in
+ * ivf_i3d_gradcam_layer, then ivf_cam_reduce for the n_kinds kinds of kinds_host and ivf_cam_resize_normalise per
+ * kind.  cam [n_kinds,b,T'*(T/T'),out_h,out_w].  The scratch is part of the plan's workspace. */
+int ivf_i3d_cam_layer(ivf_i3d_t* net, const float* x, int b, const int* target, const char* layer, int n_kinds,
+                      const int* kinds_host, int per_frame, int out_h, int out_w, float* cam, float* probs,
+                      ivf_stream_t stream);
+/* The same up to the reduction: cam [n_kinds,b,T',H',W'] un-resized, weights [n_kinds,b,C], fp32 copies of the
+ * activations and gradients the reduction read, [b,T',H',W',C], and probs [b,K]; every output optional. */
+int ivf_i3d_cam_raw(ivf_i3d_t* net, const float* x, int b, const int* target, const char* layer, int n_kinds,
+                    const int* kinds_host, float* cam, float* weights, float* feat, float* grad, float* probs,
+                    ivf_stream_t stream);
 /* argmax over K of probs [b,K] -> target [b] (np.argmax, grad_cam_videos.py:69-70). */
 int ivf_argmax(const float* probs, int b, int K, int* target, ivf_stream_t stream);
 
@@ -855,6 +892,23 @@ int ivf_clstm_gradcam(ivf_clstm_t* net, const float* x, int b, const int* target
  * gradients the reduction read, [b,n,hid,Hp,Wp] (n as above); every output optional. */
 int ivf_clstm_gradcam_raw(ivf_clstm_t* net, const float* x, int b, const int* target, int layer, float* cam,
                           float* weights, float* feat, float* grad, float* probs, ivf_stream_t stream);
+/* The Grad-CAM family on the same [B,T,hid,plane] buffers and step list as ivf_clstm_gradcam_reduce:
+ * positions = selected steps x plane; kinds, rows and rules as ivf_cam_reduce; weights [n_kinds,B,hid] (optional
+ * unless kind 0 is asked for: its kernels keep the weights there), cam [n_kinds,B,n_steps,plane]; hid <=
+ * IVF_CAM_MAX_HID.  One workgroup per clip, fixed summation order, no atomics.  The maps are post-BN and can be
+ * negative: s_k may be negative or tiny and Grad-CAM++'s denominator may pass through 0; values propagate. */
+int ivf_clstm_cam_reduce(const float* feat, const float* grad, const int* steps_host, int n_steps, int n_kinds,
+                         const int* kinds_host, float* weights, float* cam, int B, int T, int hid, int plane,
+                         ivf_stream_t stream);
+/* ivf_clstm_gradcam / ivf_clstm_gradcam_raw for n_kinds kinds from one forward and one backward:
+ * cam [n_kinds,b,n*(T/n),out_h,out_w]; raw: cam [n_kinds,b,n,Hp,Wp], weights [n_kinds,b,hid], feat and grad
+ * [b,n,hid,Hp,Wp] as ivf_clstm_gradcam_raw. */
+int ivf_clstm_cam(ivf_clstm_t* net, const float* x, int b, const int* target, int layer, int n_kinds,
+                  const int* kinds_host, int per_frame, int out_h, int out_w, float* cam, float* probs,
+                  ivf_stream_t stream);
+int ivf_clstm_cam_raw(ivf_clstm_t* net, const float* x, int b, const int* target, int layer, int n_kinds,
+                      const int* kinds_host, float* cam, float* weights, float* feat, float* grad, float* probs,
+                      ivf_stream_t stream);
 /* Workspace views of one layer after a forward / backward: pooled outputs X and their gradient dX, both
  * [b,T,hid,Hp,Wp]; every output optional. */
 int ivf_clstm_layer_buffers(ivf_clstm_t* net, int layer, const float** X, const float** dX, int* hid, int* Hp,

@@ -26,7 +26,7 @@ def find_masks(dat_loader, model, hyper_params, lam1, lam2, N, maskType="gradien
                maskSigma=None, lam3=None, maxBox=None, doIntGrad=False, igSteps=32, igBaseline="frozen", doRise=False,
                riseMasks=1024, riseProb=0.5, riseGrid=None, riseSigma=None, riseSeed=0, doSmoothGrad=False, sgSamples=32,
                sgLevel=0.15, sgSeed=0, doShapley=False, shapPerms=64, shapGrid=None, shapSigma=None, shapSeed=0,
-               doCurves=False, curveGrid=None, curveSigma=None, curveStep=1):
+               doCurves=False, curveGrid=None, curveSigma=None, curveStep=1, camKinds=(), camTarget=None):
     """smth:125-315.  maskType 'combi' runs the exhaustive one-blob search over masks of length <= maxMaskLength
     (smth:137-141, no gradient descent; N is unused); any other maskType keeps the gradient search from
     init_mask(mode="central"), which the reference hard-codes (smth:190).  maskType 'spacetime' (an extension, no
@@ -51,6 +51,10 @@ def find_masks(dat_loader, model, hyper_params, lam1, lam2, N, maskType="gradien
     shapSigma input pixels, drawn from shapSeed, forward passes only, shapPerms (cells + 1) of them per clip -- and writes a
     further pickle of records with 'ShapHeatMap' [T,H,W], 'ShapCells' and 'ShapStderr' [gt,gh,gw], 'ShapFrames' [T],
     'shap_total', 'n_perms', 'seed'.
+    camKinds (an extension as well; with doGradCam) lists further members of the activation-map family --
+    'gradcam++', 'xgradcam', 'hirescam', 'layercam' -- computed in the same call as Grad-CAM on camTarget (default: the
+    Grad-CAM target, then from the one forward and backward), returned per clip batch as cam_<kind>, written to a
+    further pickle (CamFamily in place of GradCam) of records with one [T,H,W] map per kind, and ranked by doCurves.
     doCurves (an extension as well, whatever the maskType; freeze only) also runs the deletion and insertion curves of
     every attribution the call produced -- the cells of curveGrid (gt, gh, gw) (default (T, 1, 1): the frames, ranked by
     the frame profiles; with a spatial grid by the [T,H,W] maps), blurred by curveSigma input pixels, frozen or released
@@ -67,7 +71,7 @@ def find_masks(dat_loader, model, hyper_params, lam1, lam2, N, maskType="gradien
         rise_p=riseProb, rise_grid=riseGrid, rise_sigma=riseSigma, rise_seed=riseSeed, do_smoothgrad=doSmoothGrad,
         sg_samples=sgSamples, sg_level=sgLevel, sg_seed=sgSeed, do_shapley=doShapley, shap_perms=shapPerms,
         shap_grid=shapGrid, shap_sigma=shapSigma, shap_seed=shapSeed, do_curves=doCurves, curve_grid=curveGrid,
-        curve_sigma=curveSigma, curve_step=curveStep)
+        curve_sigma=curveSigma, curve_step=curveStep, cam_kinds=camKinds, cam_target=camTarget)
 
 
 def main(argv=None):

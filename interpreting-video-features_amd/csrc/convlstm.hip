@@ -864,7 +864,7 @@ struct ivf_clstm {
   int feat;      // hid * Hp * Wp of the top layer
   int fc_in;     // endFC inputs: feat * number of output steps
   size_t ws_bytes;
-  size_t off_p, off_dp, off_flat, off_dflat, off_logits, off_probs, off_cam, off_camw, off_cammm, off_camtgt;
+  size_t off_p, off_dp, off_flat, off_dflat, off_logits, off_probs, off_cam, off_camw, off_cammm, off_camtgt, off_fam_cam, off_fam_w;
   SearchScratch sc;
   int n_cam_steps = 0;      // effective steps reached: the map stack of Grad-CAM target 'clstm'
   int cam_steps[64];
@@ -967,6 +967,9 @@ extern "C" int ivf_clstm_create(const ivf_clstm_config* c, ivf_clstm_t** out) {
   n->off_camw = takeb(B * hid * 4);
   n->off_cammm = takeb(B * T * 2 * 4);
   n->off_camtgt = takeb(B * 4);
+  // the Grad-CAM family (cam_ops.hip): the five kinds' raw maps and channel weights
+  n->off_fam_cam = takeb(5 * B * T * n->L[0].Hp * n->L[0].Wp * 4);
+  n->off_fam_w = takeb(5 * B * hid * 4);
   n->n_cam_steps = n->cfg.n_out_steps;
   for (int e = 0; e < n->cfg.n_out_steps; ++e) n->cam_steps[e] = n->cfg.out_steps[e];
   n->ws_bytes = bytes;
@@ -1467,11 +1470,10 @@ extern "C" int ivf_clstm_layer_buffers(ivf_clstm_t* n, int layer, const float** 
 
 namespace ivf {
 
-// forward, truncated backward and the reduction; leaves the raw maps [b, st->n, Hp, Wp] at off_cam and the channel
-// weights [b, hid] at off_camw.  layer -1: the stack of the effective steps of the top layer (the reference's
-// branch); 0 .. L-1: every step of that layer.
-static int clstm_cam_core(ivf_clstm* n, const float* x, int b, const int* target, int layer, float* probs,
-                          CamSteps* st, const LayerPlan** lp, hipStream_t s) {
+// forward and truncated backward of a Grad-CAM call, and the steps of its map stack.  layer -1: the stack of the
+// effective steps of the top layer (the reference's branch); 0 .. L-1: every step of that layer.
+static int clstm_cam_passes(ivf_clstm* n, const float* x, int b, const int* target, int layer, float* probs,
+                            CamSteps* st, const LayerPlan** lp, hipStream_t s) {
   const int nl = (int)n->L.size();
   IVF_CHECK_ARG(x, "clstm_gradcam: null clip");
   IVF_CHECK_ARG(layer >= -1 && layer < nl, "clstm_gradcam: layer %d outside [-1,%d)", layer, nl);
@@ -1490,8 +1492,29 @@ static int clstm_cam_core(ivf_clstm* n, const float* x, int b, const int* target
   else
     IVF_PROPAGATE(cam_steps_from(nullptr, c.T, c.T, st));
   *lp = &p;
+  return IVF_OK;
+}
+
+// the passes and the reduction; leaves the raw maps [b, st->n, Hp, Wp] at off_cam and the channel weights [b, hid]
+// at off_camw
+static int clstm_cam_core(ivf_clstm* n, const float* x, int b, const int* target, int layer, float* probs,
+                          CamSteps* st, const LayerPlan** lp, hipStream_t s) {
+  IVF_PROPAGATE(clstm_cam_passes(n, x, b, target, layer, probs, st, lp, s));
+  const LayerPlan& p = **lp;
   return ivf_clstm_gradcam_reduce(n->wsf(p.X_off), n->wsf(p.dX_off), st->s, st->n, n->at<float>(n->off_camw),
-                                  n->at<float>(n->off_cam), b, c.T, c.hidden, p.Hp * p.Wp, s);
+                                  n->at<float>(n->off_cam), b, n->cfg.T, n->cfg.hidden, p.Hp * p.Wp, s);
+}
+
+// the same for the Grad-CAM family (cam_ops.hip): maps [n_kinds, b, st->n, Hp, Wp] at off_fam_cam, weights
+// [n_kinds, b, hid] at off_fam_w, from the one forward and backward
+static int clstm_fam_core(ivf_clstm* n, const float* x, int b, const int* target, int layer, int n_kinds,
+                          const int* kinds, float* probs, CamSteps* st, const LayerPlan** lp, hipStream_t s) {
+  IVF_CHECK_ARG(kinds && n_kinds >= 1 && n_kinds <= 5, "clstm_cam: need 1..5 kinds");
+  IVF_PROPAGATE(clstm_cam_passes(n, x, b, target, layer, probs, st, lp, s));
+  const LayerPlan& p = **lp;
+  return ivf_clstm_cam_reduce(n->wsf(p.X_off), n->wsf(p.dX_off), st->s, st->n, n_kinds, kinds,
+                              n->at<float>(n->off_fam_w), n->at<float>(n->off_fam_cam), b, n->cfg.T, n->cfg.hidden,
+                              p.Hp * p.Wp, s);
 }
 
 }  // namespace ivf
@@ -1521,6 +1544,51 @@ extern "C" int ivf_clstm_gradcam_raw(ivf_clstm_t* n, const float* x, int b, cons
     IVF_CHECK_HIP(hipMemcpyAsync(cam, n->at<float>(n->off_cam), (size_t)b * st.n * plane * 4, hipMemcpyDeviceToDevice, s));
   if (weights)
     IVF_CHECK_HIP(hipMemcpyAsync(weights, n->at<float>(n->off_camw), (size_t)b * n->cfg.hidden * 4,
+                                 hipMemcpyDeviceToDevice, s));
+  const float* src[2] = {n->wsf(p->X_off), n->wsf(p->dX_off)};
+  float* dst[2] = {feat, grad};
+  for (int q = 0; q < 2; ++q)
+    if (dst[q]) {
+      const long total = (long)b * st.n * row;
+      hipLaunchKernelGGL(clstm_gather_steps_kernel, dim3(grid_for(total)), dim3(256), 0, s, src[q], st, dst[q], n->cfg.T,
+                         row, total);
+      IVF_CHECK_LAUNCH();
+    }
+  return IVF_OK;
+}
+
+extern "C" int ivf_clstm_cam(ivf_clstm_t* n, const float* x, int b, const int* target, int layer, int n_kinds,
+                             const int* kinds_host, int per_frame, int out_h, int out_w, float* cam_out, float* probs,
+                             ivf_stream_t stream) {
+  IVF_PROPAGATE(clstm_ready(n, b));
+  IVF_CHECK_ARG(cam_out && out_h > 0 && out_w > 0, "clstm_cam: bad args");
+  hipStream_t s = (hipStream_t)stream;
+  CamSteps st;
+  const LayerPlan* p = nullptr;
+  IVF_PROPAGATE(clstm_fam_core(n, x, b, target, layer, n_kinds, kinds_host, probs, &st, &p, s));
+  const int step = n->cfg.T / st.n;
+  for (int k = 0; k < n_kinds; ++k)
+    IVF_PROPAGATE(ivf_cam_resize_normalise(n->at<float>(n->off_fam_cam) + (size_t)k * b * st.n * p->Hp * p->Wp,
+                                           cam_out + (size_t)k * b * st.n * step * out_h * out_w,
+                                           n->at<float>(n->off_cammm), b, st.n, p->Hp, p->Wp, out_h, out_w, step,
+                                           per_frame, s));
+  return IVF_OK;
+}
+
+extern "C" int ivf_clstm_cam_raw(ivf_clstm_t* n, const float* x, int b, const int* target, int layer, int n_kinds,
+                                 const int* kinds_host, float* cam, float* weights, float* feat, float* grad,
+                                 float* probs, ivf_stream_t stream) {
+  IVF_PROPAGATE(clstm_ready(n, b));
+  hipStream_t s = (hipStream_t)stream;
+  CamSteps st;
+  const LayerPlan* p = nullptr;
+  IVF_PROPAGATE(clstm_fam_core(n, x, b, target, layer, n_kinds, kinds_host, probs, &st, &p, s));
+  const long plane = (long)p->Hp * p->Wp, row = plane * n->cfg.hidden;
+  if (cam)
+    IVF_CHECK_HIP(hipMemcpyAsync(cam, n->at<float>(n->off_fam_cam), (size_t)n_kinds * b * st.n * plane * 4,
+                                 hipMemcpyDeviceToDevice, s));
+  if (weights)
+    IVF_CHECK_HIP(hipMemcpyAsync(weights, n->at<float>(n->off_fam_w), (size_t)n_kinds * b * n->cfg.hidden * 4,
                                  hipMemcpyDeviceToDevice, s));
   const float* src[2] = {n->wsf(p->X_off), n->wsf(p->dX_off)};
   float* dst[2] = {feat, grad};

@@ -102,6 +102,8 @@ struct ivf_i3d {
   size_t ws_bytes = 0;
   // misc workspace offsets (bytes)
   size_t off_logits, off_probs, off_pooled, off_dpooled, off_target, off_cam, off_camw, off_mm, off_dfeat_raw;
+  // the Grad-CAM family (cam_ops.hip): maps [5,B,max_pos], weights [5,B,max_c], the reduction's scratch
+  size_t off_fam_cam = 0, off_fam_w = 0, off_fam_ws = 0;
   SearchScratch sc;
   float* warena = nullptr;
   char* ws = nullptr;
@@ -389,6 +391,15 @@ static int build_plan(ivf_i3d* n) {
   n->off_dfeat_raw = takeb(B * f.per_clip() * 4);
   if (n->stem_bwd_wide) n->off_stem_dy32 = takeb(B * n->bufs[n->ops[0].dst].per_clip() * 4);
   n->sc.carve_pairs(takeb, B, T, 12);
+  size_t max_c = 0, fam_ws = 0;       // the Grad-CAM family on any endpoint (ivf_i3d_cam_layer), behind everything else
+  for (const auto& bf : n->bufs) {
+    if (bf.name == "input" || bf.name.find('.') != std::string::npos) continue;
+    max_c = std::max(max_c, (size_t)bf.C);
+    fam_ws = std::max(fam_ws, ivf_cam_ws_bytes(c.B, bf.T * bf.H * bf.W, bf.C));
+  }
+  n->off_fam_cam = takeb(5 * B * max_pos * 4);
+  n->off_fam_w = takeb(5 * B * max_c * 4);
+  n->off_fam_ws = takeb(fam_ws);
   n->ws_bytes = bytes;
   n->loaded.assign(n->convs.size(), false);
   return IVF_OK;
@@ -1041,6 +1052,96 @@ extern "C" int ivf_i3d_gradcam_layer(ivf_i3d_t* net, const float* x, int b, cons
   IVF_PROPAGATE(gradcam_reduce(net->act(X), net->grad(X), net->act16(), wts, cm, b, npos, t.C, s));
   return ivf_cam_resize_normalise(cm, cam, net->at<float>(net->off_mm), b, t.T, t.H, t.W, out_h, out_w, c.T / t.T,
                                   per_frame, s);
+}
+
+// The Grad-CAM family (cam_ops.hip): one forward, one backward down to `layer` (the head backward alone
+// for Mixed_5c, run_backward with cam_buf otherwise, as ivf_i3d_gradcam / ivf_i3d_gradcam_layer), then the reduction
+// of every asked kind: maps [n_kinds,b,npos] at off_fam_cam, weights [n_kinds,b,C] at off_fam_w.
+static int i3d_cam_core(ivf_i3d* net, const float* x, int b, const int* target, const char* layer, int n_kinds,
+                        const int* kinds, float* probs, int* Xout, const void** feat, const void** grad,
+                        hipStream_t s) {
+  IVF_CHECK_ARG(x && target && layer && kinds, "i3d_cam: null pointer");
+  IVF_CHECK_ARG(n_kinds >= 1 && n_kinds <= 5, "i3d_cam: %d kinds, need 1..5", n_kinds);
+  int X = -1;
+  for (size_t i = 1; i < net->bufs.size(); ++i)
+    if (net->bufs[i].name == layer && net->bufs[i].name.find('.') == std::string::npos) X = (int)i;
+  if (X < 0) {
+    set_error("i3d_cam: '%s' is not an endpoint of the model (Conv3d_1a_7x7 ... Mixed_5c)", layer);
+    return IVF_ERR_BAD_ARG;
+  }
+  const ivf_i3d_config& c = net->cfg;
+  const ActBuf& t = net->bufs[X];
+  IVF_CHECK_ARG(c.T / t.T >= 1, "i3d_cam: clip shorter than the endpoint's map");
+  const int npos = t.T * t.H * t.W;
+  const void* g = nullptr;
+  if (X == net->feat_buf) {
+    IVF_PROPAGATE(ivf_i3d_forward(net, x, b, nullptr, probs, s));
+    const ConvLayer& Lh = net->convs.back();
+    float* draw = net->at<float>(net->off_dfeat_raw);
+    IVF_PROPAGATE(head_bwd(net->act(X), net->act16(), net->warena + Lh.wf_off, net->at<float>(net->off_probs), target,
+                           nullptr, nullptr, nullptr, draw, b, npos, t.C, c.num_classes, c.softmax, 0, s));
+    g = draw;
+  } else {
+    net->cam_buf = X;
+    int rc = ivf_i3d_forward(net, x, b, nullptr, probs, s);
+    if (rc == IVF_OK) rc = run_backward(net, b, target, nullptr, nullptr, s);   // stops above X, X ungated
+    net->cam_buf = -1;
+    IVF_PROPAGATE(rc);
+    g = net->grad(X);
+  }
+  *Xout = X;
+  *feat = net->act(X);
+  *grad = g;
+  return cam_reduce(net->act(X), g, net->act16(), n_kinds, kinds, net->at<float>(net->off_fam_w),
+                    net->at<float>(net->off_fam_cam), net->at<char>(net->off_fam_ws), b, npos, t.C, s);
+}
+
+extern "C" int ivf_i3d_cam_layer(ivf_i3d_t* net, const float* x, int b, const int* target, const char* layer,
+                                 int n_kinds, const int* kinds_host, int per_frame, int out_h, int out_w, float* cam,
+                                 float* probs, ivf_stream_t stream) {
+  IVF_PROPAGATE(check_ready(net, b));
+  IVF_CHECK_ARG(cam && out_h > 0 && out_w > 0, "i3d_cam_layer: bad args");
+  hipStream_t s = (hipStream_t)stream;
+  int X = -1;
+  const void *f = nullptr, *g = nullptr;
+  IVF_PROPAGATE(i3d_cam_core(net, x, b, target, layer, n_kinds, kinds_host, probs, &X, &f, &g, s));
+  const ActBuf& t = net->bufs[X];
+  const int npos = t.T * t.H * t.W, step = net->cfg.T / t.T;
+  for (int k = 0; k < n_kinds; ++k)
+    IVF_PROPAGATE(ivf_cam_resize_normalise(net->at<float>(net->off_fam_cam) + (size_t)k * b * npos,
+                                           cam + (size_t)k * b * t.T * step * out_h * out_w, net->at<float>(net->off_mm), b,
+                                           t.T, t.H, t.W, out_h, out_w, step, per_frame, s));
+  return IVF_OK;
+}
+
+extern "C" int ivf_i3d_cam_raw(ivf_i3d_t* net, const float* x, int b, const int* target, const char* layer, int n_kinds,
+                               const int* kinds_host, float* cam, float* weights, float* feat, float* grad,
+                               float* probs, ivf_stream_t stream) {
+  IVF_PROPAGATE(check_ready(net, b));
+  hipStream_t s = (hipStream_t)stream;
+  int X = -1;
+  const void* src[2] = {nullptr, nullptr};
+  IVF_PROPAGATE(i3d_cam_core(net, x, b, target, layer, n_kinds, kinds_host, probs, &X, &src[0], &src[1], s));
+  const ActBuf& t = net->bufs[X];
+  const size_t npos = (size_t)t.T * t.H * t.W, cnt = (size_t)b * npos * t.C;
+  if (cam)
+    IVF_CHECK_HIP(hipMemcpyAsync(cam, net->at<float>(net->off_fam_cam), (size_t)n_kinds * b * npos * 4,
+                                 hipMemcpyDeviceToDevice, s));
+  if (weights)
+    IVF_CHECK_HIP(hipMemcpyAsync(weights, net->at<float>(net->off_fam_w), (size_t)n_kinds * b * t.C * 4,
+                                 hipMemcpyDeviceToDevice, s));
+  float* dst[2] = {feat, grad};
+  for (int q = 0; q < 2; ++q) {
+    if (!dst[q]) continue;
+    if (net->act16()) {
+      hipLaunchKernelGGL(widen_bf16_kernel, dim3(grid_for(cnt)), dim3(256), 0, s, (const unsigned short*)src[q], dst[q],
+                         cnt);
+      IVF_CHECK_LAUNCH();
+    } else {
+      IVF_CHECK_HIP(hipMemcpyAsync(dst[q], src[q], cnt * 4, hipMemcpyDeviceToDevice, s));
+    }
+  }
+  return IVF_OK;
 }
 
 /* bytes per stored activation / gradient element of the plan's endpoints: 4, or 2 (bf16) for IVF_MATH_BF16ACT */

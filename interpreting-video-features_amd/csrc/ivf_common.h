@@ -58,6 +58,9 @@ int head_bwd(const void* feat, bool bf16, const float* w, const float* probs, co
              hipStream_t s);
 int gradcam_reduce(const void* feat, const void* grad, bool bf16, float* weights, float* cam, int B, int npos, int C,
                    hipStream_t s);
+// the Grad-CAM family (cam_ops.hip) in either storage: what ivf_cam_reduce{,_bf16} do
+int cam_reduce(const void* feat, const void* grad, bool bf16, int n_kinds, const int* kinds, float* weights,
+               float* cam, void* ws, int B, int npos, int C, hipStream_t s);
 
 #define IVF_CHECK_ARG(cond, ...)                 \
   do {                                           \

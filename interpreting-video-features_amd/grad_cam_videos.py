@@ -130,10 +130,14 @@ class GradCam:
 
 
 class GradCamVideo(GradCam):
-    """grad_cam_videos.py:46-142."""
+    """grad_cam_videos.py:46-142.  `kind` (an EXTENSION) selects another member of the activation-map
+    family on the same target layer: 'gradcam++', 'xgradcam', 'hirescam' or 'layercam'; the default 'gradcam' is the
+    reference's map on the reference's call path."""
 
     def __init__(self, model, target_layer_names, class_dict, use_cuda,
-                 input_spatial_size=224, normalizePerFrame=False, archType="I3D"):
+                 input_spatial_size=224, normalizePerFrame=False, archType="I3D", kind="gradcam"):
+        L.cam_kind_ids([kind])                              # an unknown kind is refused here, naming the five
+        self.kind = kind
         self.model = _unwrap(model)
         self.archType = archType
         self.cuda = use_cuda
@@ -165,7 +169,12 @@ class GradCamVideo(GradCam):
         if index is not None:
             target = [int(index)]                           # grad_cam_videos.py:69-72
         width, height = self.input_spatial_size             # cv2 dsize order, grad_cam_videos.py:119-120
-        cam, output = eng.gradcam(x, target, per_frame=bool(self.normalizePerFrame), out_hw=(height, width),
-                                  layer=layer)
+        if self.kind == "gradcam":
+            cam, output = eng.gradcam(x, target, per_frame=bool(self.normalizePerFrame), out_hw=(height, width),
+                                      layer=layer)
+        else:
+            cams, output = eng.cam(x, target, kinds=(self.kind,), per_frame=bool(self.normalizePerFrame),
+                                   out_hw=(height, width), layer=layer)
+            cam = cams[self.kind]
         cam_vid = cam[0].cpu().numpy().astype(np.float32)
         return cam_vid, output

@@ -944,6 +944,57 @@ class I3DEngine(_Engine):
                                                   1 if per_frame else 0, oh, ow, L.ptr(cam), L.ptr(probs), L.stream()))
         return cam, probs
 
+    def _cam_endpoint(self, layer):
+        """(T', H', W', C) of an endpoint that can be a CAM target."""
+        if "." in layer or ":" in layer or layer == "input":
+            raise L.IvfError(f"'{layer}' is not an endpoint of the model")
+        p = c_void_p()
+        v = [c_int() for _ in range(4)]
+        L.check(L.lib().ivf_i3d_endpoint(self._h, layer.encode(), byref(p), *[byref(a) for a in v], None))
+        return tuple(a.value for a in v)
+
+    def cam(self, x, target=None, kinds=("gradcam",), per_frame=True, out_hw=None, layer="Mixed_5c"):
+        """The Grad-CAM family from ONE forward and ONE backward: ({kind: cam [b,T,H,W]}, probs [b,K]) for
+        the kinds of 'gradcam', 'gradcam++', 'xgradcam', 'hirescam', 'layercam' asked for; arguments as `gradcam`."""
+        x = self._clip(x)
+        b = x.shape[0]
+        C, T, H, W = self.clip_shape
+        oh, ow = out_hw if out_hw is not None else (H, W)
+        kinds, ids = L.cam_kind_ids(kinds)
+        Tf = self._cam_endpoint(layer)[0]
+        if target is None:
+            target = self.argmax(self.forward(x))
+        tgt = self._targets(target, b)
+        cam = torch.empty(len(kinds), b, Tf * (T // Tf), oh, ow, device=self.device)
+        probs = torch.empty(b, self.K, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().ivf_i3d_cam_layer(self._h, L.ptr(x), b, L.ptr(tgt), layer.encode(), len(kinds), ids,
+                                              1 if per_frame else 0, oh, ow, L.ptr(cam), L.ptr(probs), L.stream()))
+        return {k: cam[i] for i, k in enumerate(kinds)}, probs
+
+    def cam_raw(self, x, target=None, kinds=("gradcam",), layer="Mixed_5c"):
+        """The pieces of `cam` before the resize: {kind: dict(cam [b,T',H',W'], weights [b,C])} plus, under 'feat' and
+        'grad', fp32 copies [b,T',H',W',C] of the activations and gradients the reduction read, and 'probs' [b,K]."""
+        x = self._clip(x)
+        b = x.shape[0]
+        kinds, ids = L.cam_kind_ids(kinds)
+        Tf, Hf, Wf, Cf = self._cam_endpoint(layer)
+        if target is None:
+            target = self.argmax(self.forward(x))
+        tgt = self._targets(target, b)
+        dev = self.device
+        cam = torch.empty(len(kinds), b, Tf, Hf, Wf, device=dev)
+        wts = torch.empty(len(kinds), b, Cf, device=dev)
+        out = dict(feat=torch.empty(b, Tf, Hf, Wf, Cf, device=dev), grad=torch.empty(b, Tf, Hf, Wf, Cf, device=dev),
+                   probs=torch.empty(b, self.K, device=dev))
+        with torch.cuda.device(dev):
+            L.check(L.lib().ivf_i3d_cam_raw(self._h, L.ptr(x), b, L.ptr(tgt), layer.encode(), len(kinds), ids,
+                                            L.ptr(cam), L.ptr(wts), L.ptr(out["feat"]), L.ptr(out["grad"]),
+                                            L.ptr(out["probs"]), L.stream()))
+        for i, k in enumerate(kinds):
+            out[k] = dict(cam=cam[i], weights=wts[i])
+        return out
+
 
 class CLSTMEngine(_Engine):
     """Plan + arenas for `models.CLSTM_4.Model` (reference CLSTM_4.py:69-85 over
@@ -1062,6 +1113,45 @@ class CLSTMEngine(_Engine):
             L.check(L.lib().ivf_clstm_gradcam_raw(self._h, L.ptr(x), b, L.ptr(tgt), li, L.ptr(out["cam"]),
                                                   L.ptr(out["weights"]), L.ptr(out["feat"]), L.ptr(out["grad"]),
                                                   L.ptr(out["probs"]), L.stream()))
+        return out
+
+    def cam(self, x, target=None, kinds=("gradcam",), per_frame=True, out_hw=None, layer=None):
+        """The Grad-CAM family (DESIGN 18) from ONE forward and ONE backward: ({kind: cam [b,frames,H,W]}, probs);
+        arguments as `gradcam`."""
+        x = self._clip(x)
+        b = x.shape[0]
+        C, T, H, W = self.clip_shape
+        oh, ow = out_hw if out_hw is not None else (H, W)
+        kinds, ids = L.cam_kind_ids(kinds)
+        li, n = self._cam_layer(layer)
+        tgt = self._targets(target, b) if target is not None else None
+        cam = torch.empty(len(kinds), b, n * (T // n), oh, ow, device=self.device)
+        probs = torch.empty(b, self.K, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().ivf_clstm_cam(self._h, L.ptr(x), b, L.ptr(tgt), li, len(kinds), ids, 1 if per_frame else 0,
+                                          int(oh), int(ow), L.ptr(cam), L.ptr(probs), L.stream()))
+        return {k: cam[i] for i, k in enumerate(kinds)}, probs
+
+    def cam_raw(self, x, target=None, kinds=("gradcam",), layer=None):
+        """The pieces of `cam` before the resize: {kind: dict(cam [b,n,Hp,Wp], weights [b,hid])} plus 'feat' and 'grad'
+        [b,n,hid,Hp,Wp] (what the reduction read) and 'probs' [b,K]."""
+        x = self._clip(x)
+        b = x.shape[0]
+        kinds, ids = L.cam_kind_ids(kinds)
+        li, n = self._cam_layer(layer)
+        hid, Hp, Wp = self.layer_dims(self.layers - 1 if li < 0 else li)
+        tgt = self._targets(target, b) if target is not None else None
+        dev = self.device
+        cam = torch.empty(len(kinds), b, n, Hp, Wp, device=dev)
+        wts = torch.empty(len(kinds), b, hid, device=dev)
+        out = dict(feat=torch.empty(b, n, hid, Hp, Wp, device=dev), grad=torch.empty(b, n, hid, Hp, Wp, device=dev),
+                   probs=torch.empty(b, self.K, device=dev))
+        with torch.cuda.device(dev):
+            L.check(L.lib().ivf_clstm_cam_raw(self._h, L.ptr(x), b, L.ptr(tgt), li, len(kinds), ids, L.ptr(cam),
+                                              L.ptr(wts), L.ptr(out["feat"]), L.ptr(out["grad"]), L.ptr(out["probs"]),
+                                              L.stream()))
+        for i, k in enumerate(kinds):
+            out[k] = dict(cam=cam[i], weights=wts[i])
         return out
 
 

@@ -50,8 +50,14 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                     max_box=None, do_intgrad=False, ig_steps=32, ig_baseline="frozen", do_rise=False, rise_masks=1024,
                     rise_p=0.5, rise_grid=None, rise_sigma=None, rise_seed=0, do_smoothgrad=False, sg_samples=32,
                     sg_level=0.15, sg_seed=0, do_shapley=False, shap_perms=64, shap_grid=None, shap_sigma=None,
-                    shap_seed=0, do_curves=False, curve_grid=None, curve_sigma=None, curve_step=1):
-    """do_curves (the drivers' doCurves, an extension: DESIGN 17) also runs the deletion and insertion curves of every
+                    shap_seed=0, do_curves=False, curve_grid=None, curve_sigma=None, curve_step=1, cam_kinds=(),
+                    cam_target=None):
+    """cam_kinds (the drivers' camKinds, an extension: DESIGN 18; with doGradCam) also computes the listed members of the
+    Grad-CAM family ('gradcam++', 'xgradcam', 'hirescam', 'layercam') on cam_target (default: the Grad-CAM target, then
+    from Grad-CAM's own forward and backward) and writes a further list of records -- true_class, pred_class, video_id
+    and one [T,H,W] float32 map per kind -- to a pickle named like the Grad-CAM one with CamFamily in place of GradCam;
+    do_curves ranks them under the kind's name.  Empty, nothing changes.
+    do_curves (the drivers' doCurves, an extension: DESIGN 17) also runs the deletion and insertion curves of every
     attribution the call produced (ivf_search.MaskSearch: the frame profiles on the default frame grid, the [T,H,W] maps
     on a spatial curve_grid; curve_sigma the blur in input pixels, curve_step cells per forward; freeze only) and writes
     a further list of records -- true_class, pred_class, video_id, grid, step, and per method ('time_mask' or
@@ -102,7 +108,8 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
     net.eval()                                                      # smth:145
     flt = _class_filter(classOI)
     masks, time_results, cam_results, ig_results, rise_results, sg_results = [], [], [], [], [], []
-    shap_results, curve_results = [], []
+    shap_results, curve_results, fam_results = [], [], []
+    cam_kinds = tuple(cam_kinds) if doGradCam else ()
     if write_files and not os.path.exists(results_path):
         os.makedirs(results_path)
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -133,7 +140,8 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                        do_smoothgrad=do_smoothgrad, sg_samples=sg_samples, sg_level=sg_level,
                                        sg_seed=sg_seed, do_shapley=do_shapley, shap_perms=shap_perms, shap_grid=shap_grid,
                                        shap_sigma=shap_sigma, shap_seed=shap_seed, do_curves=do_curves,
-                                       curve_grid=curve_grid, curve_sigma=curve_sigma, curve_step=curve_step)
+                                       curve_grid=curve_grid, curve_sigma=curve_sigma, curve_step=curve_step,
+                                       cam_kinds=cam_kinds, cam_target=cam_target)
         res = search.run(xs, labels[keep])
         host = {k: v.detach().cpu() for k, v in res.items()
                 if k not in ("gradcam", "box_scores", "ig_map", "rise_map", "sg_map", "sg_sq_map", "sg_var_map", "shap_map")}
@@ -215,6 +223,10 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                 cam_results.append({'true_class': true_class, 'pred_class': pred,
                                     'video_id': int(vid) if flavour == "smth" else vid,
                                     'GCHeatMap': host["gradcam"][j].numpy().astype(np.float32)})
+            if cam_kinds:
+                fam_results.append({'true_class': true_class, 'pred_class': pred,
+                                    'video_id': int(vid) if flavour == "smth" else vid,
+                                    **{k: host["cam_" + k][j].numpy().astype(np.float32) for k in cam_kinds}})
             if do_intgrad:
                 ig_results.append({'true_class': true_class, 'pred_class': pred,
                                    'video_id': int(vid) if flavour == "smth" else vid,
@@ -309,6 +321,9 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
             pickle.dump(time_results, f)
         with open(os.path.join(results_path, gname.replace(os.sep, "_")), "wb") as f:
             pickle.dump(cam_results, f)
+        if cam_kinds:
+            with open(os.path.join(results_path, gname.replace("GradCam", "CamFamily").replace(os.sep, "_")), "wb") as f:
+                pickle.dump(fam_results, f)
         if do_intgrad:
             with open(os.path.join(results_path, gname.replace("GradCam", "IntGrad").replace(os.sep, "_")), "wb") as f:
                 pickle.dump(ig_results, f)
@@ -330,6 +345,7 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
     find_masks_impl.last_sg_results = sg_results
     find_masks_impl.last_shap_results = shap_results
     find_masks_impl.last_curve_results = curve_results
+    find_masks_impl.last_cam_family_results = fam_results
     return masks
 
 

@@ -22,6 +22,9 @@ class IvfError(RuntimeError):
 
 MATH_FP32, MATH_BF16X3, MATH_BF16X6, MATH_BF16ACT = 0, 1, 2, 3
 CONV_AUTO, CONV_IGEMM_BASE, CONV_PIX4, CONV_HALO_BASE = 0, 1, 15, 16      # IVF_CONV_* (kernel variant ids)
+# IVF_CAM_* (kind ids of the Grad-CAM family, csrc/cam_ops.hip) and the chunk of its per-channel passes
+CAM_KINDS = {"gradcam": 0, "gradcam++": 1, "xgradcam": 2, "hirescam": 3, "layercam": 4}
+CAM_CHUNK = 128
 MATH_MODES = {"fp32": MATH_FP32, "bf16x3": MATH_BF16X3, "bf16x6": MATH_BF16X6, "bf16act": MATH_BF16ACT}
 
 
@@ -143,6 +146,10 @@ _SIGS = {
     "ivf_head_bwd_bf16": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ivf_gradcam_reduce": (c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "ivf_gradcam_reduce_bf16": (c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    # csrc/cam_ops.hip (Grad-CAM++ / XGrad-CAM / HiResCAM / LayerCAM, documented extension)
+    "ivf_cam_ws_bytes": (c_size_t, [_I, _I, _I]),
+    "ivf_cam_reduce": (c_int, [_P, _P, _I, POINTER(c_int), _P, _P, _P, _I, _I, _I, _P]),
+    "ivf_cam_reduce_bf16": (c_int, [_P, _P, _I, POINTER(c_int), _P, _P, _P, _I, _I, _I, _P]),
     "ivf_cam_resize_normalise": (c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ivf_argmax": (c_int, [_P, _I, _I, _P, _P]),
     "ivf_i3d_create": (c_int, [POINTER(I3DConfig), POINTER(c_void_p)]),
@@ -175,6 +182,8 @@ _SIGS = {
     "ivf_i3d_smoothgrad": (c_int, [_P, _P, _I, _P, _I, _F, _U] + [_P] * 10),
     "ivf_i3d_gradcam": (c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "ivf_i3d_gradcam_layer": (c_int, [_P, _P, _I, _P, c_char_p, _I, _I, _I, _P, _P, _P]),
+    "ivf_i3d_cam_layer": (c_int, [_P, _P, _I, _P, c_char_p, _I, POINTER(c_int), _I, _I, _I, _P, _P, _P]),
+    "ivf_i3d_cam_raw": (c_int, [_P, _P, _I, _P, c_char_p, _I, POINTER(c_int)] + [_P] * 6),
     "ivf_i3d_conv_flops_per_clip": (ctypes.c_double, [_P]),
     "ivf_conv3d_variants": (c_int, [POINTER(ConvDesc), POINTER(c_int), _I]),
     "ivf_conv3d_default_variant": (c_int, [POINTER(ConvDesc)]),
@@ -219,6 +228,9 @@ _SIGS = {
     "ivf_clstm_set_cam_steps": (c_int, [_P, POINTER(c_int), _I]),
     "ivf_clstm_gradcam": (c_int, [_P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "ivf_clstm_gradcam_raw": (c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "ivf_clstm_cam_reduce": (c_int, [_P, _P, POINTER(c_int), _I, _I, POINTER(c_int), _P, _P, _I, _I, _I, _I, _P]),
+    "ivf_clstm_cam": (c_int, [_P, _P, _I, _P, _I, _I, POINTER(c_int), _I, _I, _I, _P, _P, _P]),
+    "ivf_clstm_cam_raw": (c_int, [_P, _P, _I, _P, _I, _I, POINTER(c_int)] + [_P] * 6),
     "ivf_clstm_layer_buffers": (c_int, [_P, _I, POINTER(c_void_p), POINTER(c_void_p)] + [POINTER(c_int)] * 3),
     # csrc/tf_clstm.hip (documented extension)
     "ivf_tfclstm_create": (c_int, [POINTER(TFCLSTMConfig), POINTER(c_void_p)]),
@@ -270,6 +282,15 @@ def check(rc):
 
 
 _recent = collections.deque(maxlen=64)
+
+
+def cam_kind_ids(kinds):
+    """ctypes int array of the ids of a sequence of Grad-CAM family kind names; an unknown name raises."""
+    kinds = [kinds] if isinstance(kinds, str) else list(kinds)
+    for k in kinds:
+        if k not in CAM_KINDS:
+            raise IvfError(f"unknown CAM kind {k!r}: one of {', '.join(CAM_KINDS)}")
+    return kinds, (c_int * max(len(kinds), 1))(*[CAM_KINDS[k] for k in kinds])
 
 
 def ptr(t):

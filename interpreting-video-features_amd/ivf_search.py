@@ -246,8 +246,13 @@ class MaskSearch:
                  ig_baseline="frozen", do_rise=False, rise_masks=1024, rise_p=0.5, rise_grid=None, rise_sigma=None,
                  rise_seed=0, do_smoothgrad=False, sg_samples=32, sg_level=0.15, sg_seed=0, do_shapley=False,
                  shap_perms=64, shap_grid=None, shap_sigma=None, shap_seed=0, do_curves=False, curve_grid=None,
-                 curve_sigma=None, curve_step=1):
-        """do_curves (an extension without a counterpart in the reference): also run the deletion and
+                 curve_sigma=None, curve_step=1, cam_kinds=(), cam_target=None):
+        """cam_kinds (an extension without a counterpart in the reference; with do_gradcam): further members
+        of the activation-map family -- 'gradcam++', 'xgradcam', 'hirescam', 'layercam' -- on cam_target (an endpoint
+        name, or the ConvLSTM engine's layer; default: the Grad-CAM target, and then Grad-CAM and the extra kinds come
+        from ONE forward and ONE backward); run() then also returns cam_<kind> [b,T,H,W], and do_curves ranks them under
+        the kind's name.
+        do_curves (an extension without a counterpart in the reference): also run the deletion and
         insertion curves (Petsiuk et al. 2018) of every attribution this call produced, on the cells of curve_grid
         (gt, gh, gw) (default (T, 1, 1): the frames), blurred by curve_sigma input pixels, curve_step cells per forward.
         With a frame grid (gh = gw = 1) the attributions are the frame profiles -- time_mask (named 'st_mask' where it
@@ -295,6 +300,9 @@ class MaskSearch:
         self.mask_type, self.threshold, self.lr = mask_type, threshold, lr
         self.grad_cam_type = grad_cam_type
         self.do_gradcam, self.run_temp_mask = do_gradcam, run_temp_mask
+        self.cam_kinds, self.cam_target = L.cam_kind_ids(cam_kinds)[0], cam_target
+        if "gradcam" in self.cam_kinds:
+            raise L.IvfError("cam_kinds lists the kinds beside 'gradcam', which do_gradcam computes")
         self.normalize_per_frame = normalize_per_frame
         self.gradcam_size = gradcam_size
         self.do_intgrad, self.ig_steps, self.ig_baseline = bool(do_intgrad), ig_steps, ig_baseline   # read only when on
@@ -354,8 +362,17 @@ class MaskSearch:
                 out["traj"] = traj
         if self.do_gradcam:
             gc_target = pred if self.grad_cam_type == "guessed" else target  # smth:253,266-267
-            cam, _ = eng.gradcam(x, gc_target, per_frame=self.normalize_per_frame, out_hw=self.gradcam_size)
+            kw = dict(per_frame=self.normalize_per_frame, out_hw=self.gradcam_size)
+            if self.cam_kinds and self.cam_target is None:                   # the family from Grad-CAM's own passes
+                cams, _ = eng.cam(x, gc_target, kinds=["gradcam"] + self.cam_kinds, **kw)
+                cam = cams["gradcam"]
+            else:
+                cam, _ = eng.gradcam(x, gc_target, **kw)
+                if self.cam_kinds:
+                    cams, _ = eng.cam(x, gc_target, kinds=self.cam_kinds, layer=self.cam_target, **kw)
             out["gradcam"] = cam                                             # smth:269
+            for k in self.cam_kinds:
+                out["cam_" + k] = cams[k]
         if self.do_intgrad:
             r = eng.ig(x, target, steps=self.ig_steps, baseline=self.ig_baseline)
             for k in ("ig_map", "ig_frames", "ig_abs_frames", "ig_total", "ig_gap"):
@@ -389,8 +406,8 @@ class MaskSearch:
         if spatial:
             if "st_mask" in out:
                 attrs["st_mask"] = self.engine.st_expand(out["st_mask"], self.st_grid(x), self.mask_sigma)
-            for name, key in (("gradcam", "gradcam"), ("ig", "ig_map"), ("rise", "rise_map"), ("sg", "sg_map"),
-                              ("shap", "shap_map")):
+            for name, key in [("gradcam", "gradcam"), ("ig", "ig_map"), ("rise", "rise_map"), ("sg", "sg_map"),
+                              ("shap", "shap_map")] + [(k, "cam_" + k) for k in self.cam_kinds]:
                 if key in out and tuple(out[key].shape[1:]) == (T,) + HW:
                     attrs[name] = out[key]
             return attrs
@@ -398,6 +415,9 @@ class MaskSearch:
             attrs["st_mask" if "st_mask" in out else "time_mask"] = out["time_mask"]
         if "gradcam" in out and out["gradcam"].shape[1] == T:
             attrs["gradcam"] = out["gradcam"].float().mean(dim=(2, 3))
+        for k in self.cam_kinds:
+            if out["cam_" + k].shape[1] == T:
+                attrs[k] = out["cam_" + k].float().mean(dim=(2, 3))
         for name, key in (("ig", "ig_frames"), ("rise", "rise_frames"), ("sg", "sg_frames"), ("shap", "shap_frames")):
             if key in out:
                 attrs[name] = out[key]
