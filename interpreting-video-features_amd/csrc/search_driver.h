@@ -173,68 +173,67 @@ static int run_st_search(const Backbone& v, const float* x, int b, const int* ta
   return IVF_OK;
 }
 
-// Exhaustive one-blob search (maskType 'combi'): the b*n candidates of b clips run in chunks (for_each_chunk) --
-// stage straight into the input buffer, forward, pick the target score -- all on one stream, no host sync, no
-// allocation.
-static inline int run_blob_scores(const Backbone& v, const float* x, int b, const int* target, int max_len, int mode,
-                                  float* scores, hipStream_t s) {
-  const int n = ivf_blob_count(v.T, max_len);
-  if (n < 0) return IVF_ERR_BAD_ARG;
-  return for_each_chunk(v, (long long)b * n, [&](long long first, int cnt) -> int {
-    IVF_PROPAGATE(ivf_blob_stage(x, b, v.C, v.T, v.HW, max_len, mode, first, cnt, v.in, v.layout, s));
-    IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
-    return blob_pick(v.probs, target, v.K, n, first, cnt, scores, s);
-  });
-}
-
-// Exhaustive one-box search (maskType 'stcombi', stmask_ops.hip): run_blob_scores with the box staging -- per chunk
-// ivf_box_stage -> forward -> blob_pick, one stream, no host synchronisation, no allocation.
-static inline int run_box_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,
-                                 const float* A_W, int gh, int gw, int H, int W, int max_len, int mh, int mw,
-                                 float* scores, hipStream_t s) {
-  const long long n = ivf_box_count(v.T, max_len, gh, gw, mh, mw);
-  if (n < 0) return IVF_ERR_BAD_ARG;
-  return for_each_chunk(v, (long long)b * n, [&](long long first, int cnt) -> int {
-    IVF_PROPAGATE(ivf_box_stage(x, b, v.C, v.T, H, W, A_H, A_W, gh, gw, max_len, mh, mw, first, cnt, v.in, v.layout, s));
-    IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
-    return blob_pick(v.probs, target, v.K, (int)n, first, cnt, scores, s);
-  });
-}
-
-// RISE random-mask saliency (rise_ops.hip; an extension): run_box_scores with the random-mask staging -- per
-// chunk ivf_rise_stage -> forward -> blob_pick on the b * n (clip, mask) rows, one stream, no host synchronisation, no
-// allocation, no scratch beyond `scores`.
-static inline int run_rise_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,
-                                  const float* A_W, int gt, int gh, int gw, int H, int W, int n, unsigned seed,
-                                  unsigned thresh, float* scores, hipStream_t s) {
-  return for_each_chunk(v, (long long)b * n, [&](long long first, int cnt) -> int {
-    IVF_PROPAGATE(ivf_rise_stage(x, b, v.C, v.T, H, W, A_H, A_W, gt, gh, gw, n, seed, thresh, first, cnt, v.in, v.layout, s));
-    IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
-    return blob_pick(v.probs, target, v.K, n, first, cnt, scores, s);
-  });
-}
-
-// Shapley value sampling (shapley_ops.hip; an extension): run_rise_scores with the prefix staging -- per chunk
-// ivf_shap_stage -> forward -> blob_pick on the b * n * (P + 1) (clip, permutation, prefix) rows, ranks [n,P] the
-// caller's table; one stream, no host synchronisation, no allocation, no scratch beyond `scores`.
-static inline int run_shap_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,
-                                  const float* A_W, int gt, int gh, int gw, int H, int W, int n,
-                                  const unsigned short* ranks, float* scores, hipStream_t s) {
-  const long long per = (long long)n * ((long long)gt * gh * gw + 1);       // rows of one clip
-  if (per > 0x7fffffffLL) {
-    set_error("shap_scores: %lld rows per clip", per);
-    return IVF_ERR_BAD_ARG;
-  }
+// Scores of a flattened candidate list, `per` rows for each of b clips (scores [b,per]): per chunk (for_each_chunk)
+// stage(first, cnt) writes the rows straight into the input buffer, then forward, then blob_pick of the target score --
+// all on one stream, no host synchronisation, no allocation, no scratch beyond `scores`.  The wrappers below give the
+// row count and the staging call of each search; a count they refuse never reaches the loop.
+template <class Stage>
+static inline int run_row_scores(const Backbone& v, int b, long long per, const int* target, float* scores, hipStream_t s,
+                                 Stage&& stage) {
   return for_each_chunk(v, b * per, [&](long long first, int cnt) -> int {
-    IVF_PROPAGATE(ivf_shap_stage(x, b, v.C, v.T, H, W, A_H, A_W, gt, gh, gw, n, ranks, first, cnt, v.in, v.layout, s));
+    IVF_PROPAGATE(stage(first, cnt));
     IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
     return blob_pick(v.probs, target, v.K, (int)per, first, cnt, scores, s);
   });
 }
 
-// Deletion / insertion curves (curve_ops.hip; an extension): run_shap_scores with a rank table per clip --
-// per chunk ivf_curve_stage -> forward -> blob_pick on the b * ncurves * (J + 1) (clip, curve, j) rows, chunks crossing
-// clip and curve boundaries; one stream, no host synchronisation, no allocation, no scratch beyond `scores`.
+// Exhaustive one-blob search (maskType 'combi'): the n candidates of a clip
+static inline int run_blob_scores(const Backbone& v, const float* x, int b, const int* target, int max_len, int mode,
+                                  float* scores, hipStream_t s) {
+  const int n = ivf_blob_count(v.T, max_len);
+  if (n < 0) return IVF_ERR_BAD_ARG;
+  return run_row_scores(v, b, n, target, scores, s, [&](long long first, int cnt) {
+    return ivf_blob_stage(x, b, v.C, v.T, v.HW, max_len, mode, first, cnt, v.in, v.layout, s);
+  });
+}
+
+// Exhaustive one-box search (maskType 'stcombi', stmask_ops.hip)
+static inline int run_box_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,
+                                 const float* A_W, int gh, int gw, int H, int W, int max_len, int mh, int mw,
+                                 float* scores, hipStream_t s) {
+  const long long n = ivf_box_count(v.T, max_len, gh, gw, mh, mw);
+  if (n < 0) return IVF_ERR_BAD_ARG;
+  return run_row_scores(v, b, n, target, scores, s, [&](long long first, int cnt) {
+    return ivf_box_stage(x, b, v.C, v.T, H, W, A_H, A_W, gh, gw, max_len, mh, mw, first, cnt, v.in, v.layout, s);
+  });
+}
+
+// RISE random-mask saliency (rise_ops.hip; an extension): the n masks of a clip
+static inline int run_rise_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,
+                                  const float* A_W, int gt, int gh, int gw, int H, int W, int n, unsigned seed,
+                                  unsigned thresh, float* scores, hipStream_t s) {
+  return run_row_scores(v, b, n, target, scores, s, [&](long long first, int cnt) {
+    return ivf_rise_stage(x, b, v.C, v.T, H, W, A_H, A_W, gt, gh, gw, n, seed, thresh, first, cnt, v.in, v.layout, s);
+  });
+}
+
+// Shapley value sampling (shapley_ops.hip; an extension): the n * (P + 1) (permutation, prefix) rows of a
+// clip, ranks [n,P] the caller's table
+static inline int run_shap_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,
+                                  const float* A_W, int gt, int gh, int gw, int H, int W, int n,
+                                  const unsigned short* ranks, float* scores, hipStream_t s) {
+  const long long per = (long long)n * ((long long)gt * gh * gw + 1);
+  if (per > 0x7fffffffLL) {
+    set_error("shap_scores: %lld rows per clip", per);
+    return IVF_ERR_BAD_ARG;
+  }
+  return run_row_scores(v, b, per, target, scores, s, [&](long long first, int cnt) {
+    return ivf_shap_stage(x, b, v.C, v.T, H, W, A_H, A_W, gt, gh, gw, n, ranks, first, cnt, v.in, v.layout, s);
+  });
+}
+
+// Deletion / insertion curves (curve_ops.hip; an extension): the ncurves * (J + 1) (curve, j) rows of a clip,
+// a rank table per clip; chunks cross clip and curve boundaries
 static inline int run_curve_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,
                                    const float* A_W, int gt, int gh, int gw, int H, int W, const unsigned short* ranks,
                                    int curves, int step, float* scores, hipStream_t s) {
@@ -243,12 +242,9 @@ static inline int run_curve_scores(const Backbone& v, const float* x, int b, con
     set_error("curve_scores: need curves in 1 .. 3 (got %d) and 1 <= step (%d) <= gt gh gw (%lld) <= 4096", curves, step, P);
     return IVF_ERR_BAD_ARG;
   }
-  const long long per = (curves == 3 ? 2 : 1) * ((P + step - 1) / step + 1);       // rows of one clip
-  return for_each_chunk(v, b * per, [&](long long first, int cnt) -> int {
-    IVF_PROPAGATE(ivf_curve_stage(x, b, v.C, v.T, H, W, A_H, A_W, gt, gh, gw, ranks, curves, step, first, cnt, v.in,
-                                  v.layout, s));
-    IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
-    return blob_pick(v.probs, target, v.K, (int)per, first, cnt, scores, s);
+  const long long per = (curves == 3 ? 2 : 1) * ((P + step - 1) / step + 1);
+  return run_row_scores(v, b, per, target, scores, s, [&](long long first, int cnt) {
+    return ivf_curve_stage(x, b, v.C, v.T, H, W, A_H, A_W, gt, gh, gw, ranks, curves, step, first, cnt, v.in, v.layout, s);
   });
 }
 
@@ -268,15 +264,12 @@ struct IgScratch {
   }
 };
 
-// Scores of the b * K path points x0 + alpha[k] (x - x0), as run_blob_scores runs its candidates: per chunk
-// ivf_ig_stage -> forward -> blob_pick.  scores [b,K].
+// Scores of the K path points x0 + alpha[k] (x - x0) of a clip.  scores [b,K].
 static inline int run_ig_path_scores(const Backbone& v, const float* x, int b, const int* target, int base_kind,
                                      const float* base, float base_value, const float* alpha, int K, float* scores,
                                      hipStream_t s) {
-  return for_each_chunk(v, (long long)b * K, [&](long long first, int cnt) -> int {
-    IVF_PROPAGATE(ivf_ig_stage(x, base_kind, base, base_value, alpha, b, v.C, v.T, v.HW, K, first, cnt, v.in, v.layout, s));
-    IVF_PROPAGATE(v.forward(v.plan, cnt, nullptr, s));
-    return blob_pick(v.probs, target, v.K, K, first, cnt, scores, s);
+  return run_row_scores(v, b, K, target, scores, s, [&](long long first, int cnt) {
+    return ivf_ig_stage(x, base_kind, base, base_value, alpha, b, v.C, v.T, v.HW, K, first, cnt, v.in, v.layout, s);
   });
 }
 

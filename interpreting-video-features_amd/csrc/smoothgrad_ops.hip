@@ -21,7 +21,7 @@
 
 namespace ivf {
 
-// MurmurHash3's finaliser, as rise_ops.hip has it (restated: the two translation units share no header for it)
+// MurmurHash3's finaliser, as grid_stage.h has it (restated: the two translation units share no header for it)
 __device__ __forceinline__ unsigned sg_fmix32(unsigned h) {
   h ^= h >> 16;
   h *= 0x85EBCA6Bu;

@@ -402,11 +402,32 @@ class _Engine:
                                    L.ptr(out["ig_map"]), L.ptr(out["ig_frames"]), L.ptr(out["ig_abs_frames"]),
                                    L.ptr(out["ig_total"]), L.ptr(out["path_scores"]), L.ptr(ws), L.stream()))
         out["score_base"] = self.ig_path_scores(x, tgt, baseline, base_arg, alpha=[0.0])[:, 0]
-        idx = tgt.long().view(-1, 1)
-        out["score_x"] = torch.cat([self.forward(x[i:i + self.max_batch]).gather(1, idx[i:i + self.max_batch])
-                                    for i in range(0, b, self.max_batch)])[:, 0]
+        out["score_x"] = self._score_x(x, tgt)
         out["ig_gap"] = out["ig_total"] - (out["score_x"] - out["score_base"])
         return out
+
+    def _score_x(self, x, tgt):
+        """score [b] of tgt[clip] under the plan's ordinary forward, in chunks of max_batch clips"""
+        idx = tgt.long().view(-1, 1)
+        return torch.cat([self.forward(x[i:i + self.max_batch]).gather(1, idx[i:i + self.max_batch])
+                          for i in range(0, x.shape[0], self.max_batch)])[:, 0].contiguous()
+
+    def _grid3(self, grid, default, max_cells=None):
+        """(gt, gh, gw) of a grid-mask call (RISE, Shapley, curves), checked; grid None -> default"""
+        T = self.clip_shape[1]
+        if grid is None:
+            grid = default
+        try:
+            gt, gh, gw = (int(v) for v in grid)
+        except (TypeError, ValueError):
+            raise L.IvfError(f"grid must be (gt, gh, gw), got {grid!r}")
+        sides = 1 <= gt <= T <= 64 and 1 <= gh <= 32 and 1 <= gw <= 32
+        if max_cells is None and not sides:
+            raise L.IvfError(f"grid {(gt, gh, gw)}: need 1 <= gt <= T = {T} <= 64 and 1 <= gh, gw <= 32")
+        if max_cells is not None and not (sides and gt * gh * gw <= max_cells):
+            raise L.IvfError(f"grid {(gt, gh, gw)}: need 1 <= gt <= T = {T} <= 64, 1 <= gh, gw <= 32 and at most "
+                             f"{max_cells} cells")
+        return gt, gh, gw
 
     # -------------------------------------------------------------- RISE random-mask saliency (extension, DESIGN 14)
     def _rise_args(self, n_masks, p, grid, sigma, seed):
@@ -415,14 +436,7 @@ class _Engine:
         if not self._has_st:
             raise L.IvfError("RISE is built for the I3D and CLSTM plans only")
         C, T, H, W = self.clip_shape
-        if grid is None:
-            grid = (min(T, 8),) + default_st_grid(H, W)
-        try:
-            gt, gh, gw = (int(v) for v in grid)
-        except (TypeError, ValueError):
-            raise L.IvfError(f"grid must be (gt, gh, gw), got {grid!r}")
-        if not (1 <= gt <= T <= 64 and 1 <= gh <= 32 and 1 <= gw <= 32):
-            raise L.IvfError(f"grid {(gt, gh, gw)}: need 1 <= gt <= T = {T} <= 64 and 1 <= gh, gw <= 32")
+        gt, gh, gw = self._grid3(grid, (min(T, 8),) + default_st_grid(H, W))
         n, seed = int(n_masks), int(seed)
         if n < 1:
             raise L.IvfError(f"n_masks must be >= 1, got {n_masks}")
@@ -481,9 +495,7 @@ class _Engine:
         b = x.shape[0]
         C, T, H, W = self.clip_shape
         tgt = self._targets(target, b)
-        idx = tgt.long().view(-1, 1)
-        score_x = torch.cat([self.forward(x[i:i + self.max_batch]).gather(1, idx[i:i + self.max_batch])
-                             for i in range(0, b, self.max_batch)])[:, 0].contiguous()
+        score_x = self._score_x(x, tgt)
         scores = self.rise_scores(x, tgt, n, p, (gt, gh, gw), sigma, seed)
         cells, count, mean_drop = self.rise_reduce(scores, score_x, p, (gt, gh, gw), seed)
         kt = (torch.arange(T, device=self.device) * gt) // T
@@ -553,9 +565,7 @@ class _Engine:
                                            L.ptr(out["sq_map"]), L.ptr(out["var_map"]), L.ptr(out["sg_frames"]),
                                            L.ptr(out["sq_frames"]), L.ptr(out["var_frames"]),
                                            L.ptr(out["sample_scores"]), L.ptr(out["sigma"]), L.ptr(ws), L.stream()))
-        idx = tgt.long().view(-1, 1)
-        out["score_x"] = torch.cat([self.forward(x[i:i + self.max_batch]).gather(1, idx[i:i + self.max_batch])
-                                    for i in range(0, b, self.max_batch)])[:, 0]
+        out["score_x"] = self._score_x(x, tgt)
         return out
 
     # -------------------------------------------------------------- Shapley value sampling (extension)
@@ -564,15 +574,7 @@ class _Engine:
         are the frames."""
         if not self._has_st:
             raise L.IvfError("Shapley value sampling is built for the I3D and CLSTM plans only")
-        C, T, H, W = self.clip_shape
-        if grid is None:
-            grid = (T, 1, 1)
-        try:
-            gt, gh, gw = (int(v) for v in grid)
-        except (TypeError, ValueError):
-            raise L.IvfError(f"grid must be (gt, gh, gw), got {grid!r}")
-        if not (1 <= gt <= T <= 64 and 1 <= gh <= 32 and 1 <= gw <= 32 and gt * gh * gw <= 4096):
-            raise L.IvfError(f"grid {(gt, gh, gw)}: need 1 <= gt <= T = {T} <= 64, 1 <= gh, gw <= 32 and at most 4096 cells")
+        gt, gh, gw = self._grid3(grid, (self.clip_shape[1], 1, 1), 4096)
         try:
             n, seed = int(n_perms), int(seed)
         except (TypeError, ValueError):
@@ -646,9 +648,7 @@ class _Engine:
         b = x.shape[0]
         C, T, H, W = self.clip_shape
         tgt = self._targets(target, b)
-        idx = tgt.long().view(-1, 1)
-        score_x = torch.cat([self.forward(x[i:i + self.max_batch]).gather(1, idx[i:i + self.max_batch])
-                             for i in range(0, b, self.max_batch)])[:, 0].contiguous()
+        score_x = self._score_x(x, tgt)
         scores = self.shap_scores(x, tgt, n, (gt, gh, gw), sigma, seed, anti)
         cells, stderr, count, total = self.shap_reduce(scores, (gt, gh, gw), seed, anti)
         kt = (torch.arange(T, device=self.device) * gt) // T
@@ -667,15 +667,7 @@ class _Engine:
         """(gt, gh, gw, step, curves, order, A_H, A_W) of a curve call, checked; grid None -> (T, 1, 1): the frames."""
         if not self._has_st:
             raise L.IvfError("deletion / insertion curves are built for the I3D and CLSTM plans only")
-        C, T, H, W = self.clip_shape
-        if grid is None:
-            grid = (T, 1, 1)
-        try:
-            gt, gh, gw = (int(v) for v in grid)
-        except (TypeError, ValueError):
-            raise L.IvfError(f"grid must be (gt, gh, gw), got {grid!r}")
-        if not (1 <= gt <= T <= 64 and 1 <= gh <= 32 and 1 <= gw <= 32 and gt * gh * gw <= 4096):
-            raise L.IvfError(f"grid {(gt, gh, gw)}: need 1 <= gt <= T = {T} <= 64, 1 <= gh, gw <= 32 and at most 4096 cells")
+        gt, gh, gw = self._grid3(grid, (self.clip_shape[1], 1, 1), 4096)
         try:
             step, curves = int(step), int(curves)
         except (TypeError, ValueError):
@@ -797,9 +789,7 @@ class _Engine:
         x = self._clip(x, any_batch=True)
         b = x.shape[0]
         tgt = self._targets(target, b)
-        idx = tgt.long().view(-1, 1)
-        score_x = torch.cat([self.forward(x[i:i + self.max_batch]).gather(1, idx[i:i + self.max_batch])
-                             for i in range(0, b, self.max_batch)])[:, 0].contiguous()
+        score_x = self._score_x(x, tgt)
         ranks = self.curve_ranks(attr, (gt, gh, gw), sigma, order)
         if ranks.shape[0] != b:
             raise L.IvfError(f"need an attribution for each of the {b} clips, got {ranks.shape[0]}")

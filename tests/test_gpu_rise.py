@@ -147,6 +147,39 @@ def test_1x1x1_grid_rows_are_the_clip_or_the_frozen_clip(T, cpad):
     assert not torch.equal(frozen, clip)
 
 
+@pytest.mark.parametrize("cpad", [0, 4])
+@pytest.mark.parametrize("T", [5, 16])
+def test_a_rise_row_is_the_shapley_prefix_row_of_the_same_cells(T, cpad):
+    """One scan for every grid-mask family: RISE mask k freezes f of the P cells; under the one-permutation rank table
+    that ranks those cells 0 .. f-1 and the others f .. P-1, row f of ivf_shap_stage (n = 1) freezes the same cells and
+    must be row k of ivf_rise_stage, bit for bit.  b = 1, C = 3, 12 x 20, grid (3, 3, 4), sigma 1.5, four masks."""
+    import ivf_lib as L
+    b, C, H, W, grid, n, seed, p = 1, 3, 12, 20, (3, 3, 4), 4, 1234, 0.5
+    gt, gh, gw = grid
+    P = gt * gh * gw
+    xd = B.stage_inputs(b, C, T, H, W, key='rise').cuda()
+    AHd, AWd = SR.axis_weights(H, gh, 1.5).cuda(), SR.axis_weights(W, gw, 1.5).cuda()
+    rise = _stage(xd, AHd, AWd, (b, C, T, H, W, grid, n, seed, p), 0, n, cpad)
+    compared = 0
+    for k, frozen in enumerate(RR.bits(seed, p, n, P)):
+        f = int(frozen.sum())
+        if f == 0 or f == P:
+            continue
+        rank = np.empty(P, np.int64)
+        rank[np.flatnonzero(frozen)] = np.arange(f)
+        rank[np.flatnonzero(~frozen)] = np.arange(f, P)
+        rkd = torch.from_numpy(rank.astype(np.uint16).view(np.int16)).cuda()
+        buf, shap = guarded(tuple(rise.shape[1:]))
+        bits(shap).fill_(NAN_BITS)
+        L.check(L.lib().ivf_shap_stage(L.ptr(xd), b, C, T, H, W, L.ptr(AHd), L.ptr(AWd), gt, gh, gw, 1, L.ptr(rkd), f, 1,
+                                       L.ptr(shap), cpad, L.stream()))
+        torch.cuda.synchronize()
+        assert untouched(buf)
+        assert torch.equal(shap, rise[k]), f"mask {k} ({f} of {P} cells frozen): shap_stage row {f} is not rise_stage row {k}"
+        compared += 1
+    assert compared >= 3
+
+
 # ---------------------------------------------------------------------------------------------------- plans
 def _s16_x(clips=(21,)):
     import ivf_recipe as RC
