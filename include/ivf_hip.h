@@ -376,6 +376,37 @@ int ivf_sg_finish(const float* G1, const float* G2, int n, int b, int C, int T, 
  * 256 bytes; 0 with the message set for bad dims. */
 size_t ivf_sg_workspace_bytes(int b, int C, int T, int HW, int n);
 
+/* ------------------------------------------------------------------ Score-CAM for video (csrc/scorecam_ops.hip)
+ * An EXTENSION with no counterpart in the reference (Wang et al., CVPR-W 2020): the activation-map method
+ * that uses no gradient.  Per clip a target layer gives channel-major activations A [nc,gt,gh,gw], cells = gt gh gw <=
+ * 8192, 1 <= gt <= T <= 64, 1 <= gh, gw <= 32; frame u belongs to temporal cell kt = (u gt) / T as in the RISE section.
+ *   normalise  lo = min A_k, hi = max A_k; valid = lo, hi finite and hi > lo; the freeze plane
+ *              F_k = (hi - A_k) / (hi - lo) in fp32 (one subtraction per operand pair, one correctly rounded division),
+ *              F_k == 1 where the channel is not valid: 0 where the channel fires most, 1 where it is silent.
+ *   stage      a clip has nc + 1 rows.  Row r < nc: M[u] = A_H F_r[kt(u)] A_W^T summed and rounded as
+ *              ivf_stmask_expand_fwd does, then perturb 0 ('freeze'): P[0] = X[0], P[u] = (1 - M) X[u] + M P[u-1]
+ *              (ivf_stfreeze_fwd's expression), perturb 1 ('blank'): P[u] = (1 - M) X[u] for every u.  Row nc is the
+ *              baseline row, M == 1 exactly: every frame is frame 0 ('freeze'), +0.0 everywhere ('blank').
+ *   reduce     d_k = s_k - s_nc; a channel counts when it is valid and d_k is not NaN, any other has w_k = 0.
+ *              weights_kind 0 ('increase'): w_k = d_k.  1 ('softmax'): w_k = expf(d_k - d_max) / sum, d_max and the sum
+ *              (k ascending) over the counting channels.  cam[p] = max(sum_k w_k A[k,p], 0), k ascending, a multiply
+ *              and an add each, channels of weight 0 left out.
+ * No atomics; every sum has a fixed order, so a clip's numbers depend neither on the batch nor on the chunking.
+ *
+ * A [b,nc,cells] -> lo, hi [b,nc] (a zero as +0.0; NaN if the plane holds one), valid [b,nc] (int 0 / 1), F [b,nc,cells]. */
+int ivf_scorecam_normalise(const float* A, int b, int nc, int cells, float* lo, float* hi, int* valid, float* F,
+                           ivf_stream_t stream);
+/* Rows [first, first+count) of the flattened (clip, row) list of b clips x [b,C,T,H,W] into p; row j is clip
+ * (first+j)/(nc+1), row (first+j)%(nc+1) of it; count <= 65535.  F [b,nc,gt,gh,gw] in [0, 1]; out_cpad, A_H, A_W as
+ * ivf_rise_stage.  Under perturb 0 the rows r < nc equal (==) what ivf_stmask_expand_fwd followed by ivf_stfreeze_fwd
+ * write for the row's explicit per-frame S (S[u] = F_r[kt(u)]); neither S nor M is ever in memory. */
+int ivf_scorecam_stage(const float* x, int b, int C, int T, int H, int W, const float* A_H, const float* A_W, int gt,
+                       int gh, int gw, const float* F, int nc, int perturb, long long first, int count, float* p,
+                       int out_cpad, ivf_stream_t stream);
+/* scores [b,nc+1], A [b,nc,cells], valid [b,nc] -> weights_out [b,nc], cam_out [b,cells]. */
+int ivf_scorecam_reduce(const float* scores, const float* A, const int* valid, int b, int nc, int cells, int weights_kind,
+                        float* weights_out, float* cam_out, ivf_stream_t stream);
+
 /* Clip ingest: the arithmetic of ImLoader.__getitem__ /
  * KTHImLoader.__getitem__ after the JPEG decode (data_loader_jpg.py:29-37,
  * data_loader_kth.py:25-44): uint8 frames [B][T][H][W][C] -> float32 (exact), permuted to
@@ -716,6 +747,13 @@ int ivf_i3d_shap_scores(ivf_i3d_t* net, const float* x, int b, const int* target
 int ivf_i3d_curve_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
                          int gt, int gh, int gw, const unsigned short* ranks, int curves, int step, float* scores,
                          ivf_stream_t stream);
+/* Scores of the nc + 1 Score-CAM rows of each of b clips (extension, see ivf_scorecam_*): scores [b,nc+1] =
+ * probs[target[clip]] of the clip perturbed by the expanded plane of channel k of F [b,nc,gt,gh,gw], the last the
+ * baseline row, in chunks of the plan's B rows across clip boundaries (ivf_scorecam_stage -> forward -> pick); b may
+ * exceed B.  One stream, no host synchronisation, no allocation, no scratch beyond scores. */
+int ivf_i3d_scorecam_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
+                            int gt, int gh, int gw, const float* F, int nc, int perturb, float* scores,
+                            ivf_stream_t stream);
 
 /* Integrated Gradients of b clips through this plan (extension, see ivf_ig_*): the b*K path points run in chunks of the
  * plan's B rows across clip boundaries (ivf_ig_stage -> forward -> backward -> ivf_ig_accumulate), then ivf_ig_finish;
@@ -851,6 +889,10 @@ int ivf_clstm_shap_scores(ivf_clstm_t* net, const float* x, int b, const int* ta
 int ivf_clstm_curve_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
                            int gt, int gh, int gw, const unsigned short* ranks, int curves, int step, float* scores,
                            ivf_stream_t stream);
+/* ivf_i3d_scorecam_scores with the ConvLSTM backbone (rows staged NCTHW). */
+int ivf_clstm_scorecam_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H,
+                              const float* A_W, int gt, int gh, int gw, const float* F, int nc, int perturb,
+                              float* scores, ivf_stream_t stream);
 
 /* Integrated Gradients of b clips through this plan (extension, see ivf_ig_*): the b*K path points run in chunks of the
  * plan's B rows across clip boundaries (ivf_ig_stage -> forward -> backward -> ivf_ig_accumulate), then ivf_ig_finish;

@@ -26,8 +26,15 @@ def find_masks(dat_loader, model, hyper_params, lam1, lam2, N, maskType="gradien
                maskSigma=None, lam3=None, maxBox=None, doIntGrad=False, igSteps=32, igBaseline="frozen", doRise=False,
                riseMasks=1024, riseProb=0.5, riseGrid=None, riseSigma=None, riseSeed=0, doSmoothGrad=False, sgSamples=32,
                sgLevel=0.15, sgSeed=0, doShapley=False, shapPerms=64, shapGrid=None, shapSigma=None, shapSeed=0,
-               doCurves=False, curveGrid=None, curveSigma=None, curveStep=1, camKinds=(), camTarget=None):
-    """smth:125-315.  maskType 'combi' runs the exhaustive one-blob search over masks of length <= maxMaskLength
+               doCurves=False, curveGrid=None, curveSigma=None, curveStep=1, camKinds=(), camTarget=None,
+               doScoreCam=False, scoreCamTarget=None, scoreCamWeights="increase", scoreCamPerturb="freeze",
+               scoreCamSigma=None, scoreCamChannels=None):
+    """smth:125-315.  doScoreCam (an extension; whatever the maskType) also runs Score-CAM on scoreCamTarget
+    (default: the Grad-CAM target; scoreCamChannels = (first, count) a window of its channels) -- a forward pass per
+    channel with the channel's normalised map as the mask, blurred by scoreCamSigma input pixels, applied as
+    scoreCamPerturb 'freeze' or 'blank', weighted as scoreCamWeights 'increase' or 'softmax' -- and writes a further
+    pickle (ScoreCam in place of GradCam) of records with 'ScoreCamHeatMap', 'ScoreCamWeights', 'ScoreCamValid',
+    'score_base', 'layer', 'weights', 'perturb'; doCurves ranks it under 'scorecam'.  maskType 'combi' runs the exhaustive one-blob search over masks of length <= maxMaskLength
     (smth:137-141, no gradient descent; N is unused); any other maskType keeps the gradient search from
     init_mask(mode="central"), which the reference hard-codes (smth:190).  maskType 'spacetime' (an extension, no
     counterpart in the reference) searches a mask per frame and cell of a maskGrid (gh, gw) grid, blurred by maskSigma
@@ -71,7 +78,9 @@ def find_masks(dat_loader, model, hyper_params, lam1, lam2, N, maskType="gradien
         rise_p=riseProb, rise_grid=riseGrid, rise_sigma=riseSigma, rise_seed=riseSeed, do_smoothgrad=doSmoothGrad,
         sg_samples=sgSamples, sg_level=sgLevel, sg_seed=sgSeed, do_shapley=doShapley, shap_perms=shapPerms,
         shap_grid=shapGrid, shap_sigma=shapSigma, shap_seed=shapSeed, do_curves=doCurves, curve_grid=curveGrid,
-        curve_sigma=curveSigma, curve_step=curveStep, cam_kinds=camKinds, cam_target=camTarget)
+        curve_sigma=curveSigma, curve_step=curveStep, cam_kinds=camKinds, cam_target=camTarget,
+        do_scorecam=doScoreCam, scorecam_target=scoreCamTarget, scorecam_weights=scoreCamWeights,
+        scorecam_perturb=scoreCamPerturb, scorecam_sigma=scoreCamSigma, scorecam_channels=scoreCamChannels)
 
 
 def main(argv=None):

@@ -963,6 +963,17 @@ extern "C" int ivf_i3d_curve_scores(ivf_i3d_t* net, const float* x, int b, const
                           scores, (hipStream_t)stream);
 }
 
+// Score-CAM (scorecam_ops.hip): run_scorecam_scores, rows staged straight into the input buffer.
+extern "C" int ivf_i3d_scorecam_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H,
+                                       const float* A_W, int gt, int gh, int gw, const float* F, int nc, int perturb,
+                                       float* scores, ivf_stream_t stream) {
+  IVF_PROPAGATE(check_ready(net, 1));
+  IVF_CHECK_ARG(x && target && A_H && A_W && F && scores, "i3d_scorecam_scores: null pointer");
+  IVF_CHECK_ARG(b > 0 && nc > 0, "i3d_scorecam_scores: bad batch %d or channel count %d", b, nc);
+  return run_scorecam_scores(backbone(net), x, b, target, A_H, A_W, gt, gh, gw, net->cfg.H, net->cfg.W, F, nc, perturb,
+                             scores, (hipStream_t)stream);
+}
+
 // Integrated Gradients (ig_ops.hip): run_ig / run_ig_path_scores on this plan; scratch from the caller.
 extern "C" int ivf_i3d_ig(ivf_i3d_t* net, const float* x, int b, const int* target, int base_kind, const float* base,
                           float base_value, const float* alpha, const float* w, int K, float* ig_map, float* frames,

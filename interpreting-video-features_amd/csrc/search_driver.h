@@ -248,6 +248,16 @@ static inline int run_curve_scores(const Backbone& v, const float* x, int b, con
   });
 }
 
+// Score-CAM (scorecam_ops.hip; an extension): the nc channel rows of a clip and its baseline row, F
+// [b,nc,gt,gh,gw] the freeze planes
+static inline int run_scorecam_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,
+                                      const float* A_W, int gt, int gh, int gw, int H, int W, const float* F, int nc,
+                                      int perturb, float* scores, hipStream_t s) {
+  return run_row_scores(v, b, (long long)nc + 1, target, scores, s, [&](long long first, int cnt) {
+    return ivf_scorecam_stage(x, b, v.C, v.T, H, W, A_H, A_W, gt, gh, gw, F, nc, perturb, first, cnt, v.in, v.layout, s);
+  });
+}
+
 // ---------------------------------------------------------------- Integrated Gradients (ig_ops.hip)
 // An extension without a counterpart in the reference.  Its scratch belongs to the CALLER (ivf_ig_workspace_bytes), so
 // no plan's workspace size or carve order moves.

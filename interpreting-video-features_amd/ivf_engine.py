@@ -508,6 +508,124 @@ class _Engine:
         return dict(rise_scores=scores, rise_cells=cells, rise_count=count, rise_mean_drop=mean_drop, score_x=score_x,
                     rise_map=self.st_expand(S, (gh, gw), sigma), rise_frames=frames)
 
+    # -------------------------------------------------------------- Score-CAM (extension)
+    SCORECAM_WEIGHTS = {"increase": 0, "softmax": 1}
+    SCORECAM_PERTURB = {"freeze": 0, "blank": 1}
+    SCORECAM_MAX_SIDE, SCORECAM_MAX_CELLS = 32, 8192
+
+    def _scorecam_feat(self, layer):
+        """(name, (nc, gt, gh, gw), feat) of a Score-CAM target layer; feat(x) -> A [b,nc,gt,gh,gw] of at most max_batch
+        clips.  Each backbone names its layers as its Grad-CAM does."""
+        raise L.IvfError("Score-CAM is built for the I3D and CLSTM plans only")
+
+    @staticmethod
+    def _scorecam_kind(table, what, value):
+        if value not in table:
+            raise L.IvfError(f"Score-CAM {what} must be one of {', '.join(repr(k) for k in table)}, got {value!r}")
+        return table[value]
+
+    def _scorecam_layer(self, layer, channels):
+        """(name, first, nc, gt, gh, gw, feat) of a call, checked against the limits of ivf_scorecam_stage"""
+        name, (C, gt, gh, gw), feat = self._scorecam_feat(layer)
+        T = self.clip_shape[1]
+        if not (1 <= gt <= T <= 64 and gh <= self.SCORECAM_MAX_SIDE and gw <= self.SCORECAM_MAX_SIDE
+                and gt * gh * gw <= self.SCORECAM_MAX_CELLS):
+            raise L.IvfError(f"Score-CAM target {name}: its map {gt}x{gh}x{gw} exceeds the limits gt <= T = {T} <= 64, "
+                             f"gh, gw <= {self.SCORECAM_MAX_SIDE} and gt gh gw <= {self.SCORECAM_MAX_CELLS}")
+        first, nc = 0, C
+        if channels is not None:
+            try:
+                first, nc = (int(v) for v in channels)
+            except (TypeError, ValueError):
+                raise L.IvfError(f"channels must be (first, count), got {channels!r}")
+            if not (0 <= first and 1 <= nc and first + nc <= C):
+                raise L.IvfError(f"channels {(first, nc)} outside the {C} channels of {name}")
+        return name, first, nc, gt, gh, gw, feat
+
+    def scorecam_planes(self, x, layer=None, channels=None):
+        """The activations a Score-CAM call perturbs with and what ivf_scorecam_normalise makes of them: dict of A
+        [b,nc,gt,gh,gw] (channel-major fp32 copies of the layer's activations under the plan's ordinary forward; with
+        channels = (first, count) that window of them), lo, hi [b,nc], valid [b,nc] (int32) and the freeze planes F
+        [b,nc,gt,gh,gw].  b may exceed max_batch."""
+        _, first, nc, gt, gh, gw, feat = self._scorecam_layer(layer, channels)
+        x = self._clip(x, any_batch=True)
+        b = x.shape[0]
+        A = torch.cat([feat(x[i:i + self.max_batch])[:, first:first + nc] for i in range(0, b, self.max_batch)])
+        A = L.f32c(A)
+        dev = self.device
+        out = dict(A=A, lo=torch.empty(b, nc, device=dev), hi=torch.empty(b, nc, device=dev),
+                   valid=torch.empty(b, nc, dtype=torch.int32, device=dev), F=torch.empty_like(A))
+        with torch.cuda.device(dev):
+            L.check(L.lib().ivf_scorecam_normalise(L.ptr(A), b, nc, gt * gh * gw, L.ptr(out["lo"]), L.ptr(out["hi"]),
+                                                   L.ptr(out["valid"]), L.ptr(out["F"]), L.stream()))
+        return out
+
+    def scorecam_scores(self, x, target, F, sigma=None, perturb="freeze"):
+        """Scores [b,nc+1] of target[clip] with the clip perturbed by each plane of F [b,nc,gt,gh,gw] (expanded as
+        st_expand expands it), the last the baseline row: ivf_*_scorecam_scores, forward only, chunks of the plan's
+        max_batch rows across clip boundaries; b may exceed max_batch."""
+        mode = self._scorecam_kind(self.SCORECAM_PERTURB, "perturb", perturb)
+        x = self._clip(x, any_batch=True)
+        b = x.shape[0]
+        L.require_gpu(F)
+        F = L.f32c(F)
+        if F.dim() != 5 or F.shape[0] != b:
+            raise L.IvfError(f"F must be [{b},nc,gt,gh,gw], got {tuple(F.shape)}")
+        nc, gt, gh, gw = F.shape[1:]
+        _, _, _, AH, AW = self._st_axes((gh, gw), sigma)
+        tgt = self._targets(target, b)
+        scores = torch.empty(b, nc + 1, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(self._fn("scorecam_scores")(self._h, L.ptr(x), b, L.ptr(tgt), L.ptr(AH), L.ptr(AW), gt, gh, gw, L.ptr(F),
+                                                nc, mode, L.ptr(scores), L.stream()))
+        return scores
+
+    def scorecam_reduce(self, scores, A, valid, weights="increase"):
+        """ivf_scorecam_reduce on scores [b,nc+1], A [b,nc,gt,gh,gw] and valid [b,nc]: (weights [b,nc], cam [b,gt,gh,gw])."""
+        kind = self._scorecam_kind(self.SCORECAM_WEIGHTS, "weights", weights)
+        L.require_gpu(scores, A, valid)
+        s, A = L.f32c(scores), L.f32c(A)
+        valid = valid.to(torch.int32).contiguous()
+        b, nc, gt, gh, gw = A.shape
+        if tuple(s.shape) != (b, nc + 1) or tuple(valid.shape) != (b, nc):
+            raise L.IvfError(f"need scores [{b},{nc + 1}] and valid [{b},{nc}], got {tuple(s.shape)} and {tuple(valid.shape)}")
+        w = torch.empty(b, nc, device=s.device)
+        cam = torch.empty(b, gt, gh, gw, device=s.device)
+        with torch.cuda.device(s.device):
+            L.check(L.lib().ivf_scorecam_reduce(L.ptr(s), L.ptr(A), L.ptr(valid), b, nc, gt * gh * gw, kind, L.ptr(w),
+                                                L.ptr(cam), L.stream()))
+        return w, cam
+
+    def scorecam(self, x, target, layer=None, weights="increase", perturb="freeze", sigma=None, channels=None,
+                 per_frame=True, out_hw=None):
+        """Score-CAM (Wang et al. 2020) of target[clip] on b clips, b may exceed max_batch: every channel of `layer`
+        (named as the backbone's Grad-CAM names it; `channels` = (first, count) a window of them) is normalised to a
+        freeze plane, expanded to the clip (`sigma` as st_expand) and applied as the per-pixel freeze ('freeze') or as a
+        multiplicative mask on a zero baseline ('blank'); a channel's weight is its row's score above the baseline
+        row's ('increase') or the softmax of those ('softmax'); the map is relu(sum_k w_k A_k), resized and normalised
+        as the Grad-CAM of the same layer.  Returns a dict of device tensors: scorecam_map [b,frames,H,W], scorecam_cam
+        [b,gt,gh,gw], scorecam_weights [b,nc], scorecam_scores [b,nc+1], scorecam_valid [b,nc], score_x [b] (the plan's
+        ordinary forward) and score_base [b] (the baseline row)."""
+        self._scorecam_kind(self.SCORECAM_WEIGHTS, "weights", weights)        # refuse before any forward
+        self._scorecam_kind(self.SCORECAM_PERTURB, "perturb", perturb)
+        x = self._clip(x, any_batch=True)
+        b = x.shape[0]
+        C, T, H, W = self.clip_shape
+        oh, ow = out_hw if out_hw is not None else (H, W)
+        tgt = self._targets(target, b)
+        planes = self.scorecam_planes(x, layer, channels)
+        gt, gh, gw = planes["A"].shape[2:]
+        scores = self.scorecam_scores(x, tgt, planes["F"], sigma, perturb)
+        w, cam = self.scorecam_reduce(scores, planes["A"], planes["valid"], weights)
+        step = T // gt
+        out = torch.empty(b, gt * step, oh, ow, device=self.device)
+        mm = torch.empty(b, gt, 2, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().ivf_cam_resize_normalise(L.ptr(cam), L.ptr(out), L.ptr(mm), b, gt, gh, gw, int(oh), int(ow),
+                                                     step, 1 if per_frame else 0, L.stream()))
+        return dict(scorecam_map=out, scorecam_cam=cam, scorecam_weights=w, scorecam_scores=scores,
+                    scorecam_valid=planes["valid"], score_x=self._score_x(x, tgt), score_base=scores[:, -1].contiguous())
+
     # -------------------------------------------------------------- SmoothGrad / SmoothGrad^2 / VarGrad (extension, DESIGN 15)
     def _sg_args(self, n_samples, level, seed):
         """(n, level, seed) of a SmoothGrad call, checked"""
@@ -985,6 +1103,12 @@ class I3DEngine(_Engine):
             out[k] = dict(cam=cam[i], weights=wts[i])
         return out
 
+    def _scorecam_feat(self, layer):
+        layer = "Mixed_5c" if layer is None else layer
+        Tf, Hf, Wf, Cf = self._cam_endpoint(layer)
+        return (f"'{layer}'", (Cf, Tf, Hf, Wf),
+                lambda x: self.cam_raw(x, None, layer=layer)["feat"].permute(0, 4, 1, 2, 3))
+
 
 class CLSTMEngine(_Engine):
     """Plan + arenas for `models.CLSTM_4.Model` (reference CLSTM_4.py:69-85 over
@@ -1143,6 +1267,12 @@ class CLSTMEngine(_Engine):
         for i, k in enumerate(kinds):
             out[k] = dict(cam=cam[i], weights=wts[i])
         return out
+
+    def _scorecam_feat(self, layer):
+        li, n = self._cam_layer(layer)
+        hid, Hp, Wp = self.layer_dims(self.layers - 1 if li < 0 else li)
+        return ("'clstm'" if li < 0 else f"'cell{li}'", (hid, n, Hp, Wp),
+                lambda x: self.cam_raw(x, None, layer=layer)["feat"].permute(0, 2, 1, 3, 4))
 
 
 class TFCLSTMEngine(_Engine):

@@ -51,8 +51,18 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                     rise_p=0.5, rise_grid=None, rise_sigma=None, rise_seed=0, do_smoothgrad=False, sg_samples=32,
                     sg_level=0.15, sg_seed=0, do_shapley=False, shap_perms=64, shap_grid=None, shap_sigma=None,
                     shap_seed=0, do_curves=False, curve_grid=None, curve_sigma=None, curve_step=1, cam_kinds=(),
-                    cam_target=None):
-    """cam_kinds (the drivers' camKinds, an extension: DESIGN 18; with doGradCam) also computes the listed members of the
+                    cam_target=None, do_scorecam=False, scorecam_target=None, scorecam_weights="increase",
+                    scorecam_perturb="freeze", scorecam_sigma=None, scorecam_channels=None):
+    """do_scorecam (the drivers' doScoreCam, an extension: DESIGN 19) also runs Score-CAM of the target's score on
+    scorecam_target (default: the Grad-CAM target; scorecam_channels = (first, count) a window of its channels, each
+    normalised, expanded with a blur of scorecam_sigma input pixels and applied as scorecam_perturb 'freeze' or 'blank',
+    weighted as scorecam_weights 'increase' or 'softmax'; forward passes only) and writes a further list of records --
+    true_class, pred_class, video_id, ScoreCamHeatMap [frames,H,W], ScoreCamWeights, ScoreCamValid [nc], score_base, layer,
+    weights, perturb -- to a pickle named like the Grad-CAM one with ScoreCam in place of GradCam; with the strips on, a
+    further set of heat-map strips (folder `scorecam` beside `combined`) blends the map; its plan holds at least
+    blob_batch clips so that the channel rows of a loader batch fill it; do_curves ranks the map under 'scorecam'.  The
+    multi-GPU record gather (ivf_shard) does not carry these records.  Off, nothing changes.
+    cam_kinds (the drivers' camKinds, an extension: DESIGN 18; with doGradCam) also computes the listed members of the
     Grad-CAM family ('gradcam++', 'xgradcam', 'hirescam', 'layercam') on cam_target (default: the Grad-CAM target, then
     from Grad-CAM's own forward and backward) and writes a further list of records -- true_class, pred_class, video_id
     and one [T,H,W] float32 map per kind -- to a pickle named like the Grad-CAM one with CamFamily in place of GradCam;
@@ -108,7 +118,7 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
     net.eval()                                                      # smth:145
     flt = _class_filter(classOI)
     masks, time_results, cam_results, ig_results, rise_results, sg_results = [], [], [], [], [], []
-    shap_results, curve_results, fam_results = [], [], []
+    shap_results, curve_results, fam_results, scorecam_results = [], [], [], []
     cam_kinds = tuple(cam_kinds) if doGradCam else ()
     if write_files and not os.path.exists(results_path):
         os.makedirs(results_path)
@@ -128,7 +138,7 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
             continue
         xs = x[keep].contiguous()
         eng = net._engine_for(xs, min_batch=blob_batch) if mask_mode in ("combi", "stcombi") or do_rise or do_smoothgrad \
-            or do_shapley or do_curves else net._engine_for(xs)
+            or do_shapley or do_curves or do_scorecam else net._engine_for(xs)
         search = ivf_search.MaskSearch(eng, lam1, lam2, N, temporalMaskType, threshold=0.9, lr=0.2,
                                        grad_cam_type=hyper_params.get("gradCamType", "guessed"),
                                        do_gradcam=doGradCam, run_temp_mask=runTempMask,
@@ -141,10 +151,14 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                        sg_seed=sg_seed, do_shapley=do_shapley, shap_perms=shap_perms, shap_grid=shap_grid,
                                        shap_sigma=shap_sigma, shap_seed=shap_seed, do_curves=do_curves,
                                        curve_grid=curve_grid, curve_sigma=curve_sigma, curve_step=curve_step,
-                                       cam_kinds=cam_kinds, cam_target=cam_target)
+                                       cam_kinds=cam_kinds, cam_target=cam_target, do_scorecam=do_scorecam,
+                                       scorecam_target=scorecam_target, scorecam_weights=scorecam_weights,
+                                       scorecam_perturb=scorecam_perturb, scorecam_sigma=scorecam_sigma,
+                                       scorecam_channels=scorecam_channels)
         res = search.run(xs, labels[keep])
         host = {k: v.detach().cpu() for k, v in res.items()
-                if k not in ("gradcam", "box_scores", "ig_map", "rise_map", "sg_map", "sg_sq_map", "sg_var_map", "shap_map")}
+                if k not in ("gradcam", "box_scores", "ig_map", "rise_map", "sg_map", "sg_sq_map", "sg_var_map", "shap_map",
+                            "scorecam_map")}
         spacetime = runTempMask and mask_mode in ("spacetime", "stcombi")
         st_maps = eng.st_expand(res["st_mask"], search.st_grid(xs), mask_sigma) if spacetime and write_files and visualise \
             else None
@@ -185,6 +199,12 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                 pos = res["shap_map"].clamp_min(0.0)
                 top = pos.amax(dim=(2, 3), keepdim=True)
                 shap_heat = torch.where(top > 0, pos / torch.where(top > 0, top, torch.ones_like(top)), torch.zeros_like(pos))
+        scorecam_heat = None
+        if do_scorecam:
+            host["scorecam_map"] = res["scorecam_map"].detach().cpu()
+            if runTempMask and write_files and visualise and res["scorecam_map"].shape[1] == xs.shape[2]:
+                # the map is normalised to [0,1] as the Grad-CAM map is; a constant slice (NaN there) stays all zero
+                scorecam_heat = torch.nan_to_num(res["scorecam_map"], nan=0.0).clamp(0.0, 1.0)
         for j, bi in enumerate(keep):
             true_class = int(labels[bi])
             pred = int(host["pred_class"][j])
@@ -261,6 +281,14 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                      'ShapFrames': host["shap_frames"][j].numpy().astype(np.float32),
                                      'shap_total': float(host["shap_total"][j]),
                                      'n_perms': int(shap_perms), 'seed': int(shap_seed)})
+            if do_scorecam:
+                scorecam_results.append({'true_class': true_class, 'pred_class': pred,
+                                         'video_id': int(vid) if flavour == "smth" else vid,
+                                         'ScoreCamHeatMap': host["scorecam_map"][j].numpy().astype(np.float32),
+                                         'ScoreCamWeights': host["scorecam_weights"][j].numpy().astype(np.float32),
+                                         'ScoreCamValid': host["scorecam_valid"][j].numpy().astype(bool),
+                                         'score_base': float(host["scorecam_score_base"][j]), 'layer': scorecam_target,
+                                         'weights': scorecam_weights, 'perturb': scorecam_perturb})
             if do_curves:
                 T_ = xs.shape[2]
                 rec = {'true_class': true_class, 'pred_class': pred, 'video_id': int(vid) if flavour == "smth" else vid,
@@ -302,6 +330,11 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                     for kind in ("freeze", "reverse"):
                         viz.create_image_arrays(xs, shap_heat[j], tmask, j, kind, os.path.join(os.path.dirname(d), "shapley"),
                                                 str(vid), 0, xs.shape[4], xs.shape[3])
+                if scorecam_heat is not None:
+                    for kind in ("freeze", "reverse"):
+                        viz.create_image_arrays(xs, scorecam_heat[j], tmask, j, kind,
+                                                os.path.join(os.path.dirname(d), "scorecam"), str(vid), 0, xs.shape[4],
+                                                xs.shape[3])
                 if flavour != "smth":
                     import mask as _mask
                     pert = st_pert[j] if st_pert is not None else _mask.perturb_sequence(xs, tmask, temporalMaskType)[j]
@@ -336,6 +369,9 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
         if do_shapley:
             with open(os.path.join(results_path, gname.replace("GradCam", "Shapley").replace(os.sep, "_")), "wb") as f:
                 pickle.dump(shap_results, f)
+        if do_scorecam:
+            with open(os.path.join(results_path, gname.replace("GradCam", "ScoreCam").replace(os.sep, "_")), "wb") as f:
+                pickle.dump(scorecam_results, f)
         if do_curves:
             with open(os.path.join(results_path, gname.replace("GradCam", "Curves").replace(os.sep, "_")), "wb") as f:
                 pickle.dump(curve_results, f)
@@ -346,6 +382,7 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
     find_masks_impl.last_shap_results = shap_results
     find_masks_impl.last_curve_results = curve_results
     find_masks_impl.last_cam_family_results = fam_results
+    find_masks_impl.last_scorecam_results = scorecam_results
     return masks
 
 

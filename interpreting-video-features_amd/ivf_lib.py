@@ -116,6 +116,10 @@ _SIGS = {
     "ivf_curve_ranks": (c_int, [_P] + [_I] * 7 + [_P, _P]),
     "ivf_curve_stage": (c_int, [_P] + [_I] * 5 + [_P, _P] + [_I] * 3 + [_P, _I, _I, ctypes.c_longlong, _I, _P, _I, _P]),
     "ivf_curve_reduce": (c_int, [_P] + [_I] * 5 + [_P] * 3),
+    # csrc/scorecam_ops.hip (Score-CAM, documented extension)
+    "ivf_scorecam_normalise": (c_int, [_P, _I, _I, _I] + [_P] * 5),
+    "ivf_scorecam_stage": (c_int, [_P] + [_I] * 5 + [_P, _P] + [_I] * 3 + [_P, _I, _I, ctypes.c_longlong, _I, _P, _I, _P]),
+    "ivf_scorecam_reduce": (c_int, [_P] * 3 + [_I] * 4 + [_P] * 3),
     # csrc/ig_ops.hip (Integrated Gradients, documented extension)
     "ivf_ig_stage": (c_int, [_P, _I, _P, _F, _P] + [_I] * 5 + [ctypes.c_longlong, _I, _P, _I, _P]),
     "ivf_ig_accumulate": (c_int, [_P, _I, _P, _I, ctypes.c_longlong, _I, _P] + [_I] * 4 + [_P]),
@@ -179,6 +183,7 @@ _SIGS = {
     "ivf_i3d_rise_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_U, _U, _P, _P]),
     "ivf_i3d_shap_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_P, _P, _P]),
     "ivf_i3d_curve_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 3 + [_P, _I, _I, _P, _P]),
+    "ivf_i3d_scorecam_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 3 + [_P, _I, _I, _P, _P]),
     "ivf_i3d_smoothgrad": (c_int, [_P, _P, _I, _P, _I, _F, _U] + [_P] * 10),
     "ivf_i3d_gradcam": (c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "ivf_i3d_gradcam_layer": (c_int, [_P, _P, _I, _P, c_char_p, _I, _I, _I, _P, _P, _P]),
@@ -223,6 +228,7 @@ _SIGS = {
     "ivf_clstm_rise_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_U, _U, _P, _P]),
     "ivf_clstm_shap_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_P, _P, _P]),
     "ivf_clstm_curve_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 3 + [_P, _I, _I, _P, _P]),
+    "ivf_clstm_scorecam_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 3 + [_P, _I, _I, _P, _P]),
     "ivf_clstm_smoothgrad": (c_int, [_P, _P, _I, _P, _I, _F, _U] + [_P] * 10),
     "ivf_clstm_gradcam_reduce": (c_int, [_P, _P, POINTER(c_int), _I, _P, _P, _I, _I, _I, _I, _P]),
     "ivf_clstm_set_cam_steps": (c_int, [_P, POINTER(c_int), _I]),

@@ -246,8 +246,16 @@ class MaskSearch:
                  ig_baseline="frozen", do_rise=False, rise_masks=1024, rise_p=0.5, rise_grid=None, rise_sigma=None,
                  rise_seed=0, do_smoothgrad=False, sg_samples=32, sg_level=0.15, sg_seed=0, do_shapley=False,
                  shap_perms=64, shap_grid=None, shap_sigma=None, shap_seed=0, do_curves=False, curve_grid=None,
-                 curve_sigma=None, curve_step=1, cam_kinds=(), cam_target=None):
-        """cam_kinds (an extension without a counterpart in the reference; with do_gradcam): further members
+                 curve_sigma=None, curve_step=1, cam_kinds=(), cam_target=None, do_scorecam=False, scorecam_target=None,
+                 scorecam_weights="increase", scorecam_perturb="freeze", scorecam_sigma=None, scorecam_channels=None):
+        """do_scorecam (an extension without a counterpart in the reference): also run Score-CAM of the
+        target's score on scorecam_target (an endpoint name, or the ConvLSTM engine's layer; default: the Grad-CAM
+        target) -- every channel (or the window scorecam_channels = (first, count)) normalised, expanded to the clip
+        (blurred by scorecam_sigma input pixels) and applied as scorecam_perturb ('freeze' or 'blank'), weighted as
+        scorecam_weights ('increase' or 'softmax'), forward passes only; run() then also returns scorecam_map
+        [b,frames,H,W] (resized and normalised as the Grad-CAM map), scorecam_cam, scorecam_weights, scorecam_valid and
+        scorecam_score_base [b], and do_curves ranks the map under 'scorecam'.
+        cam_kinds (an extension without a counterpart in the reference; with do_gradcam): further members
         of the activation-map family -- 'gradcam++', 'xgradcam', 'hirescam', 'layercam' -- on cam_target (an endpoint
         name, or the ConvLSTM engine's layer; default: the Grad-CAM target, and then Grad-CAM and the extra kinds come
         from ONE forward and ONE backward); run() then also returns cam_<kind> [b,T,H,W], and do_curves ranks them under
@@ -323,6 +331,12 @@ class MaskSearch:
         self.curve_grid, self.curve_sigma, self.curve_step = curve_grid, curve_sigma, curve_step
         if self.do_curves and mask_type != "freeze":
             raise L.IvfError("deletion / insertion curves perturb by freezing only")
+        self.do_scorecam = bool(do_scorecam)                                                          # read only when on
+        self.scorecam_target, self.scorecam_weights, self.scorecam_perturb = scorecam_target, scorecam_weights, scorecam_perturb
+        self.scorecam_sigma, self.scorecam_channels = scorecam_sigma, scorecam_channels
+        if self.do_scorecam:
+            engine._scorecam_kind(engine.SCORECAM_WEIGHTS, "weights", scorecam_weights)
+            engine._scorecam_kind(engine.SCORECAM_PERTURB, "perturb", scorecam_perturb)
 
     def run(self, x, labels, want_traj=False):
         """x [b,C,T,H,W] float32 on the GPU, labels [b] ints.  Returns a dict of device
@@ -378,6 +392,13 @@ class MaskSearch:
             for k in ("ig_map", "ig_frames", "ig_abs_frames", "ig_total", "ig_gap"):
                 out[k] = r[k]
             out["ig_score_base"] = r["score_base"]
+        if self.do_scorecam:
+            sc = eng.scorecam(x, target, layer=self.scorecam_target, weights=self.scorecam_weights,
+                              perturb=self.scorecam_perturb, sigma=self.scorecam_sigma, channels=self.scorecam_channels,
+                              per_frame=self.normalize_per_frame, out_hw=self.gradcam_size)
+            for k in ("scorecam_map", "scorecam_cam", "scorecam_weights", "scorecam_valid"):
+                out[k] = sc[k]
+            out["scorecam_score_base"] = sc["score_base"]
         if self.do_rise:
             grid = self.rise_grid
             if grid is None:
@@ -407,7 +428,7 @@ class MaskSearch:
             if "st_mask" in out:
                 attrs["st_mask"] = self.engine.st_expand(out["st_mask"], self.st_grid(x), self.mask_sigma)
             for name, key in [("gradcam", "gradcam"), ("ig", "ig_map"), ("rise", "rise_map"), ("sg", "sg_map"),
-                              ("shap", "shap_map")] + [(k, "cam_" + k) for k in self.cam_kinds]:
+                              ("shap", "shap_map"), ("scorecam", "scorecam_map")] + [(k, "cam_" + k) for k in self.cam_kinds]:
                 if key in out and tuple(out[key].shape[1:]) == (T,) + HW:
                     attrs[name] = out[key]
             return attrs
@@ -418,6 +439,8 @@ class MaskSearch:
         for k in self.cam_kinds:
             if out["cam_" + k].shape[1] == T:
                 attrs[k] = out["cam_" + k].float().mean(dim=(2, 3))
+        if "scorecam_map" in out and out["scorecam_map"].shape[1] == T:
+            attrs["scorecam"] = out["scorecam_map"].float().mean(dim=(2, 3))
         for name, key in (("ig", "ig_frames"), ("rise", "rise_frames"), ("sg", "sg_frames"), ("shap", "shap_frames")):
             if key in out:
                 attrs[name] = out[key]
