@@ -86,6 +86,36 @@ __device__ __forceinline__ void box_pos(int row, int hw_pitch, int* t, int* h, i
   }
 }
 
+// Narrow row order of a 4 x TH x 8 box whose map ends within its first 4 columns (the W-edge boxes of the 28 x 28
+// maps): a 32-row MFMA tile is TWO h-rows of the box across its 4 planes (4 t x 2 h x 4 w), so ceil(TH / 2) tiles
+// cover the live half of the box and the others issue nothing (see the live-tile mask in the kernel).  Lane bits
+// feed t and the low two bits of w as in box_pos; the bit that picks the w half there picks the h-row of the pair
+// here.  Rows with h >= TH (the second half of the last tile of a 7-row box, every later tile) are not part of the
+// box: the kernel clamps their LDS address into it and stores nothing for them.
+struct BoxPos { int t, h, w; };
+__host__ __device__ constexpr BoxPos narrow_box_pos(int row) {
+  const int li = row & 31, q = li >> 2, ql = q & 3;
+  const int sel = ((ql + 1) >> 1) & 1;
+  return BoxPos{(q >> 2) ? 3 - sel : sel, 2 * (row >> 5) + (ql >> 1), li & 3};
+}
+// the rows of a box that the narrow order keeps (h < TH) hit every (t < 4, h < TH, w < 4) exactly once
+template <int TH>
+constexpr bool narrow_order_is_exact() {
+  bool seen[4 * TH * 4] = {};
+  int n = 0;
+  for (int row = 0; row < 4 * TH * 8; ++row) {
+    const BoxPos p = narrow_box_pos(row);
+    if (p.t < 0 || p.t >= 4 || p.w < 0 || p.w >= 4 || p.h < 0) return false;
+    if (p.h >= TH) continue;
+    const int k = (p.t * TH + p.h) * 4 + p.w;
+    if (seen[k]) return false;
+    seen[k] = true;
+    ++n;
+  }
+  return n == 4 * TH * 4;
+}
+static_assert(narrow_order_is_exact<8>() && narrow_order_is_exact<7>(), "narrow row order must be injective onto t<4, h<TH, w<4");
+
 // LDS rows per halo plane.  The 4 x 8 x 8 boxes want the plane stride = 4 (mod 8) rows (see
 // box_pos): 100 for k = 3 as it is, 121 -> 124 for k = 4, 81 -> 84 for k = 2 (pad rows are
 // never staged nor read).
@@ -146,7 +176,11 @@ __global__ __launch_bounds__((TT * TH * TW / WROWS) * (BN / WCOLS) * KS * 64) vo
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: tap decode and tile bases stay on the scalar unit
   const int wk = wave / (WM * WN);               // tap group of this wave
-  const int wm = (wave % (WM * WN)) / WN, wn = wave % WN;
+  // A workgroup's waves go to the four SIMDs cyclically (MI355X_MICROARCH.md), so wave % 4 names a wave's SIMD.  With
+  // two column halves the half alternates with the h-row PAIR: then the live waves are spread evenly over the SIMDs
+  // when the box's last h-rows are dead (any even number of them) and also when one column half is (see below).
+  const int wm = (wave % (WM * WN)) / WN;
+  const int wn = WN == 2 ? (wave & 1) ^ ((wm >> 1) & 1) : wave % WN;
   const int li = lane & 31, lh = lane >> 5;
 
   // tile decode: n-tile fastest, then w, h, t, b
@@ -162,14 +196,43 @@ __global__ __launch_bounds__((TT * TH * TW / WROWS) * (BN / WCOLS) * KS * 64) vo
   const int t0 = tt * TT, h0 = th * TH, w0 = tw * TW;
   const int n0 = nt * BN;
 
+  // Live waves (wave-uniform, kept in scalars).  A box that hangs over the map's H edge, or a column tile past Cout,
+  // holds 32-row x 32-column MFMA tiles that nobody stores: a wave ALL of whose tiles are such issues no fragment reads
+  // and no MFMAs.  It still stages the halo, streams the weights and meets every barrier.
+  // In a 4 x TH x 8 box MFMA row tile k is h-row k of the box (box_pos), or, in a box whose map ends within its first
+  // 4 columns, h-rows {2k, 2k + 1} of its live half (narrow_box_pos; the depth-to-space epilogue keeps the standard
+  // order).  The operands and the order of every stored value's sum are those of a fully live box.
+  // (A wave with live AND dead tiles -- 64-row wave tiles, 96-column wave tiles over 288 + 32 columns -- computes them
+  // all: a second, tile-masked copy of the tap loop costs the wide tiles 20-30 registers, and the 16-wave 192-column
+  // tile, which sits at its 128, went from 20 to 292 bytes of scratch with it.)
+  constexpr bool EDGE_TILES = TT == 4 && TW == 8;
+  bool narrow = false;
+  int live_tiles = WM * TM;
+  if constexpr (EDGE_TILES) {
+    const int live_h = min(TH, a.Ho - h0);
+    narrow = !a.d2s && a.Wo - w0 <= 4;
+    live_tiles = narrow ? (live_h + 1) >> 1 : live_h;
+  }
+  const bool wave_live = wm * TM < live_tiles && n0 + wn * WCOLS < a.Cout;
+  // box row -> (t, h, w) in the order this workgroup runs; h >= TH marks a row outside the box (narrow order only)
+  auto row_pos = [&](int row, int* t, int* h, int* w) __attribute__((always_inline)) {
+    box_pos<TT, TH, TW>(row, HW, t, h, w);
+    if constexpr (EDGE_TILES) {
+      if (narrow) {
+        const BoxPos p = narrow_box_pos(row);
+        *t = p.t, *h = p.h, *w = p.w;
+      }
+    }
+  };
+
   // A-fragment base rows of this lane (one per 32-row MFMA tile of the wave)
   int arow[TM];
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
     int r = wm * WROWS + i * 32 + li;
     int pt, ph, pw;
-    box_pos<TT, TH, TW>(r, HW, &pt, &ph, &pw);
-    arow[i] = pt * PS + ph * HW + pw;
+    row_pos(r, &pt, &ph, &pw);
+    arow[i] = pt * PS + min(ph, TH - 1) * HW + pw;   // (a row outside the box is never stored: any address inside the halo does)
   }
   const int ntaps = a.kT * a.kH * a.kW;
   const int ntg = (ntaps + KS - 1) / KS;         // tap group g handles taps [g*ntg, (g+1)*ntg)
@@ -325,7 +388,8 @@ __global__ __launch_bounds__((TT * TH * TW / WROWS) * (BN / WCOLS) * KS * 64) vo
   constexpr bool PIPELINED = (TM == 1 && TN == 1);
   auto mma_tap = [&](int step, int buf, int nks) __attribute__((always_inline)) {
     const int lt0 = step * TPS;
-    const int nsub = min(TPS, min(ntg - lt0, ntaps - wk * ntg - lt0));   // valid taps of this wave's group in the step
+    // valid taps of this wave's group in the step; none for a wave without a live tile
+    const int nsub = wave_live ? min(TPS, min(ntg - lt0, ntaps - wk * ntg - lt0)) : 0;
     if (nsub <= 0) return;
     const unsigned char* bstep = b_base + (size_t)(buf * TPS * KS + wk) * NPB * BN * ROWB_B;   // + sub * KS * NPB * BN * ROWB_B
     if constexpr (PIPELINED) {   // (a partial last chunk runs all NKS slices: channels past Cin are staged as zeros)
@@ -482,7 +546,8 @@ __global__ __launch_bounds__((TT * TH * TW / WROWS) * (BN / WCOLS) * KS * 64) vo
     // group 0 adds them and owns the epilogue
     float* red = reinterpret_cast<float*>(smem);
     const int slot = (wm * WN + wn) * TM * TN;
-    if (wk == 1) {
+    // (the two waves of an output sub-tile are live or dead together; a dead one's sums are never stored)
+    if (wk == 1 && wave_live) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -491,7 +556,7 @@ __global__ __launch_bounds__((TT * TH * TW / WROWS) * (BN / WCOLS) * KS * 64) vo
           for (int r = 0; r < 16; ++r) red[((slot + i * TN + j) * 16 + r) * 64 + lane] = acc[i][j][r];
     }
     __syncthreads();
-    if (wk == 0) {
+    if (wk == 0 && wave_live) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -539,15 +604,15 @@ __global__ __launch_bounds__((TT * TH * TW / WROWS) * (BN / WCOLS) * KS * 64) vo
     IVF_STAMP_ADD(4, st_begin + 1, st_begin);      // workgroup count
     return;
   }
-  if (wk != 0) return;
+  if (wk != 0 || !wave_live) return;   // (every row or every column of a wave without a live tile is outside the output)
 
   conv_epilogue<AM, TM, TN>(
       a, acc,
       [&](int row) {
         int pt, ph, pw;
-        box_pos<TT, TH, TW>(row, HW, &pt, &ph, &pw);
+        row_pos(row, &pt, &ph, &pw);
         int t = t0 + pt, h = h0 + ph, w = w0 + pw;
-        if (t >= a.To || h >= a.Ho || w >= a.Wo) return -1;
+        if (ph >= TH || t >= a.To || h >= a.Ho || w >= a.Wo) return -1;
         return ((b * a.To + t) * a.Ho + h) * a.Wo + w;
       },
       wm * WROWS, n0 + wn * WCOLS, li, lh);
