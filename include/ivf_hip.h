@@ -334,6 +334,67 @@ int ivf_curve_stage(const float* x, int b, int C, int T, int H, int W, const flo
 int ivf_curve_reduce(const float* scores, int b, int ncurves, int curves, int P, int step, float* auc, float* auc_norm,
                      ivf_stream_t stream);
 
+/* ------------------------------------------------------------------ linear surrogates: KernelSHAP and LIME (csrc/linsur_ops.hip)
+ * An EXTENSION with no counterpart in the reference (Lundberg & Lee 2017, Ribeiro et al. 2016): a linear
+ * model of the score drop in the frozen cells, fitted by least squares in fp64 on the device.  The players are the
+ * P = gt gh gw cells of a grid as in the Shapley section above, 2 <= P <= 1024.  z_kc = 1: sample row k freezes cell c.
+ * The n sample rows are the same for every clip and are kept as packed bits, bits [n, ceil(P/32)] (uint32): bit c % 32
+ * of word c / 32 holds z_kc, the unused high bits are zero.  A clip has the n sample rows and one further row n with
+ * every cell frozen: scores [b,n+1].  The fitted quantity is y_bk = (double)score_x[b] - (double)scores[b,k], so that a
+ * cell's coefficient is > 0 where freezing it lowers the score.
+ *
+ * KernelSHAP rows [first_k, first_k+count): with h the hash and rank_k the table of the Shapley section,
+ *   s_k = 1 + #{i : h(seed, base_k, P) >= size_table[i]},  size_table [P-2] (uint32) the caller's: floor(2^32 CDF(i)),
+ *   i = 1 .. P-2, of q(s) ~ 1 / (s (P-s)) on 1 .. P-1 (the Shapley kernel's size distribution; may be null at P = 2),
+ * and row k freezes the cells with rank_k[c] < s_k.  paired = 1: an odd k is the complement of row k-1 (base_k = k-1,
+ * the rank reversed, s_k = P - s_{k-1}); else base_k = k.  sizes [count] (uint16) = s_k. */
+int ivf_kshap_rows(unsigned seed, int paired, int first_k, int count, int gt, int gh, int gw, const unsigned* size_table,
+                   unsigned* bits, unsigned short* sizes, ivf_stream_t stream);
+/* LIME rows [first_k, first_k+count): bit c of row k = h(seed, k, c) < thresh, the bits of ivf_rise_masks. */
+int ivf_lime_rows(unsigned seed, unsigned thresh, int first_k, int count, int gt, int gh, int gw, unsigned* bits,
+                  ivf_stream_t stream);
+/* Rows [first, first+count) of the flattened (clip, row) list of b clips x [b,C,T,H,W] into p: row r is clip r / (n+1)
+ * under sample row r % (n+1) of bits [n, ceil(P/32)], row n every cell frozen; count <= 65535.  out_cpad, A_H, A_W as
+ * ivf_rise_stage.  The rows equal (==) what ivf_stmask_expand_fwd followed by ivf_stfreeze_fwd write for the row's
+ * explicit per-frame S; neither S nor M is ever in memory. */
+int ivf_lin_stage(const float* x, int b, int C, int T, int H, int W, const float* A_H, const float* A_W, int gt, int gh,
+                  int gw, int n, const unsigned* bits, long long first, int count, float* p, int out_cpad,
+                  ivf_stream_t stream);
+/* The fp64 moments of the weighted least-squares problem from scores [b,n+1], score_x [b] and bits [n, ceil(P/32)]
+ * (here 1 <= P <= 1024), every element one chain in ascending k, products rounded before they are added, no atomics:
+ *   w_k = wtab[popcount(row k)] (wtab [P+1] fp64 on the device; null: w_k = 1) -> wrow [n]
+ *   N [P,P] = sum_k w_k [z_kc & z_kc'],  v [P] = sum_k w_k z_kc,  Wsum [1] = sum_k w_k,
+ *   r [b,P] = sum_k fl(w_k y_bk) z_kc,   t [b] = sum_k fl(w_k y_bk),
+ * a row that does not set a bit adds nothing.  ok [b] (int) = 0 where score_x[b] or any of the clip's n+1 scores is
+ * not finite, else 1.  All outputs are the caller's. */
+int ivf_lin_moments(const float* scores, const float* score_x, const unsigned* bits, const double* wtab, int b, int n,
+                    int P, double* N, double* v, double* Wsum, double* r, double* t, double* wrow, int* ok,
+                    ivf_stream_t stream);
+/* Bytes of the caller's factor workspace of ivf_lin_solve for P players; 0 with the message set for a bad P. */
+size_t ivf_lin_workspace_bytes(int P);
+/* The fit from the moments.  kind 0, KernelSHAP (2 <= P): the efficiency constraint sum_c phi_c = total_b =
+ * score_x[b] - scores[b,n] eliminated through the last cell l = P-1, m = P-1 unknowns,
+ *   A[c,c'] = N[c,c'] - N[c,l] - N[l,c'] + N[l,l],   rhs[b,c] = (r[b,c] - r[b,l]) - total_b (N[c,l] - N[l,l]),
+ *   phi_l = total_b - sum_{c<l} phi_c (ascending c, fp64), intercept 0.
+ * kind 1, LIME (1 <= P): the weighted ridge regression with a free intercept, m = P unknowns, mu = v / Wsum,
+ *   G[c,c'] = N[c,c'] - Wsum (mu_c mu_c') + ridge [c == c'],   rhs[b,c] = r[b,c] - mu_c t_b,
+ *   intercept[b] = t_b / Wsum - sum_c mu_c phi_c (ascending c, fp64).
+ * The system is factored once by a blocked right-looking Cholesky in fp64 (fixed summation order, no atomics) and
+ * solved for the b right-hand sides.  A pivot d_j <= 2^-20 A_jj (A_jj the entry before the factorisation) or a pivot
+ * that is not finite marks the system singular: ok = 0 and NaN cells for EVERY clip.  ok [b] is in/out (ivf_lin_moments
+ * wrote it): a clip with ok == 0 gets NaN cells and intercept.  cells [b,P] and intercept [b] are fp32, each the
+ * fp64 solution rounded once; total [b] = (float)total_b.  work: ivf_lin_workspace_bytes(P) bytes, 8-byte aligned. */
+int ivf_lin_solve(int kind, const double* N, const double* v, const double* Wsum, const double* r, const double* t,
+                  const float* scores, const float* score_x, int b, int n, int P, double ridge, void* work, float* cells,
+                  float* intercept, float* total, int* ok, ivf_stream_t stream);
+/* Fit quality r2 [b] = 1 - sum_k w_k (y_bk - yhat_bk)^2 / sum_k w_k (y_bk - t_b / Wsum)^2, yhat_bk = intercept[b] +
+ * sum_c cells[b,c] z_kc (ascending c) from the fp32 outputs widened to fp64 (intercept null: 0), wrow [n] as
+ * ivf_lin_moments wrote it (null: 1); each sum one chain in ascending k.  NaN where the denominator is 0 or
+ * ok[b] == 0. */
+int ivf_lin_fit(const float* scores, const float* score_x, const unsigned* bits, const double* wrow, const float* cells,
+                const float* intercept, const double* t, const double* Wsum, const int* ok, int b, int n, int P, float* r2,
+                ivf_stream_t stream);
+
 /* ------------------------------------------------------------------ SmoothGrad, SmoothGrad^2, VarGrad (csrc/smoothgrad_ops.hip)
  * An EXTENSION with no counterpart in the reference (Smilkov et al. 2017, Hooker et al. 2019): n noisy
  * samples x + sigma z_k of a clip x [b,C,T,HW], one forward and backward each, and per input element the first two
@@ -740,6 +801,12 @@ int ivf_i3d_rise_scores(ivf_i3d_t* net, const float* x, int b, const int* target
  * allocation, no scratch beyond scores. */
 int ivf_i3d_shap_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
                         int gt, int gh, int gw, int n, const unsigned short* ranks, float* scores, ivf_stream_t stream);
+/* Scores of the n+1 linear-surrogate rows of each of b clips (extension, see ivf_lin_*): scores [b,n+1] =
+ * probs[target[clip]] of the clip frozen per pixel by sample row k of bits [n, ceil(P/32)] (on the device), entry n the
+ * fully frozen clip, in chunks of the plan's B rows (ivf_lin_stage -> forward -> pick); b may exceed B.  One stream, no
+ * host synchronisation, no allocation, no scratch beyond scores. */
+int ivf_i3d_lin_scores(ivf_i3d_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
+                       int gt, int gh, int gw, int n, const unsigned* bits, float* scores, ivf_stream_t stream);
 /* Scores of the deletion / insertion rows of each of b clips (extension, see ivf_curve_*): scores [b,ncurves,J+1] =
  * probs[target[clip]] of the clip frozen per pixel by row j of each curve under the clip's own table ranks [b,P], in
  * chunks of the plan's B rows across clip and curve boundaries (ivf_curve_stage -> forward -> pick); b may exceed B.
@@ -885,6 +952,9 @@ int ivf_clstm_rise_scores(ivf_clstm_t* net, const float* x, int b, const int* ta
 /* ivf_i3d_shap_scores with the ConvLSTM backbone (rows staged NCTHW). */
 int ivf_clstm_shap_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
                           int gt, int gh, int gw, int n, const unsigned short* ranks, float* scores, ivf_stream_t stream);
+/* ivf_i3d_lin_scores with the ConvLSTM backbone (rows staged NCTHW). */
+int ivf_clstm_lin_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
+                         int gt, int gh, int gw, int n, const unsigned* bits, float* scores, ivf_stream_t stream);
 /* ivf_i3d_curve_scores with the ConvLSTM backbone (rows staged NCTHW). */
 int ivf_clstm_curve_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H, const float* A_W,
                            int gt, int gh, int gw, const unsigned short* ranks, int curves, int step, float* scores,

@@ -24,8 +24,19 @@ def find_masks(dat_loader, model, config, lam1, lam2, N, ita=1, maskType="gradie
                sgLevel=0.15, sgSeed=0, doShapley=False, shapPerms=64, shapGrid=None, shapSigma=None, shapSeed=0,
                doCurves=False, curveGrid=None, curveSigma=None, curveStep=1, camKinds=(), camTarget=None,
                doScoreCam=False, scoreCamTarget=None, scoreCamWeights="increase", scoreCamPerturb="freeze",
-               scoreCamSigma=None, scoreCamChannels=None):
-    """KTH:126-380.  doScoreCam (an extension; whatever the maskType) also runs Score-CAM on scoreCamTarget
+               scoreCamSigma=None, scoreCamChannels=None, doKernelShap=False, kshapSamples=256, kshapGrid=None,
+               kshapSigma=None, kshapSeed=0, doLime=False, limeSamples=1024, limeProb=0.5, limeGrid=None, limeSigma=None,
+               limeSeed=0, limeWidth=0.25, limeRidge=1.0):
+    """KTH:126-380.  doKernelShap and doLime (extensions; whatever the maskType; freeze only) also fit a linear
+    surrogate of the score drop in the frozen cells of kshapGrid / limeGrid (gt, gh, gw) (default (T, 1, 1): the frames),
+    blurred by kshapSigma / limeSigma input pixels, forward passes only, the least-squares fit in fp64 on the device --
+    KernelSHAP on kshapSamples paired coalitions with Shapley-kernel sizes drawn from kshapSeed (the values sum to the
+    score drop of the fully frozen clip), LIME on limeSamples rows that freeze a cell with probability limeProb, drawn from
+    limeSeed, weighted by an exponential kernel of width limeWidth, with ridge limeRidge and a free intercept -- and write
+    further pickles (KernelShap, Lime in place of GradCam) of records with 'KshapHeatMap' [T,H,W], 'KshapCells'
+    [gt,gh,gw], 'KshapFrames' [T], 'kshap_total', 'kshap_ok', 'kshap_r2', 'n_samples', 'seed', and 'LimeHeatMap',
+    'LimeCells', 'LimeFrames', 'lime_intercept', 'lime_ok', 'lime_r2', 'n_samples', 'seed'; doCurves ranks the maps under
+    'kshap' and 'lime'.  doScoreCam (an extension; whatever the maskType) also runs Score-CAM on scoreCamTarget
     (default: the Grad-CAM target; scoreCamChannels = (first, count) a window of its channels) -- a forward pass per
     channel with the channel's normalised map as the mask, blurred by scoreCamSigma input pixels, applied as
     scoreCamPerturb 'freeze' or 'blank', weighted as scoreCamWeights 'increase' or 'softmax' -- and writes a further
@@ -74,7 +85,10 @@ def find_masks(dat_loader, model, config, lam1, lam2, N, ita=1, maskType="gradie
         shap_grid=shapGrid, shap_sigma=shapSigma, shap_seed=shapSeed, do_curves=doCurves, curve_grid=curveGrid,
         curve_sigma=curveSigma, curve_step=curveStep, cam_kinds=camKinds, cam_target=camTarget,
         do_scorecam=doScoreCam, scorecam_target=scoreCamTarget, scorecam_weights=scoreCamWeights,
-        scorecam_perturb=scoreCamPerturb, scorecam_sigma=scoreCamSigma, scorecam_channels=scoreCamChannels)
+        scorecam_perturb=scoreCamPerturb, scorecam_sigma=scoreCamSigma, scorecam_channels=scoreCamChannels,
+        do_kernelshap=doKernelShap, kshap_samples=kshapSamples, kshap_grid=kshapGrid, kshap_sigma=kshapSigma,
+        kshap_seed=kshapSeed, do_lime=doLime, lime_samples=limeSamples, lime_p=limeProb, lime_grid=limeGrid,
+        lime_sigma=limeSigma, lime_seed=limeSeed, lime_width=limeWidth, lime_ridge=limeRidge)
 
 
 def build_model(config, args, device):

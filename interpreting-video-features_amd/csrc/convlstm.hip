@@ -1365,6 +1365,18 @@ extern "C" int ivf_clstm_shap_scores(ivf_clstm_t* net, const float* x, int b, co
                          (hipStream_t)stream);
 }
 
+// Linear surrogates (linsur_ops.hip): run_lin_scores, rows staged straight into the input buffer.
+extern "C" int ivf_clstm_lin_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H,
+                                    const float* A_W, int gt, int gh, int gw, int n, const unsigned* bits, float* scores,
+                                    ivf_stream_t stream) {
+  IVF_CHECK_ARG(net && x && target && A_H && A_W && bits && scores, "clstm_lin_scores: null pointer");
+  IVF_PROPAGATE(clstm_ready(net, 1));
+  IVF_CHECK_ARG(b > 0 && n > 0, "clstm_lin_scores: bad batch %d or row count %d", b, n);
+  IVF_CHECK_ARG(gt > 0 && gh > 0 && gw > 0, "clstm_lin_scores: bad grid (%d, %d, %d)", gt, gh, gw);
+  return run_lin_scores(backbone(net), x, b, target, A_H, A_W, gt, gh, gw, net->cfg.H, net->cfg.W, n, bits, scores,
+                        (hipStream_t)stream);
+}
+
 // Deletion / insertion curves (curve_ops.hip): run_curve_scores, rows staged straight into the input buffer.
 extern "C" int ivf_clstm_curve_scores(ivf_clstm_t* net, const float* x, int b, const int* target, const float* A_H,
                                       const float* A_W, int gt, int gh, int gw, const unsigned short* ranks, int curves,

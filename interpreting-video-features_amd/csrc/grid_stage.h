@@ -23,6 +23,7 @@ namespace ivf {
 
 constexpr int GRID_MAX_SIDE = 32;       // gh, gw: the bits of a grid row are one 32-bit word
 constexpr int GRID_MAX_PLAYERS = 4096;  // ranks fit in uint16, a row's keys in 16 KiB of LDS
+constexpr int LIN_MAX_PLAYERS = 1024;   // linear surrogates (linsur_ops.hip): the fp64 normal matrix is [P,P], 8 MiB
 
 struct Grid3 {
   int gt, gh, gw;

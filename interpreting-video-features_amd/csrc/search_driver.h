@@ -232,6 +232,16 @@ static inline int run_shap_scores(const Backbone& v, const float* x, int b, cons
   });
 }
 
+// Linear surrogates (linsur_ops.hip; an extension): the n sample rows of a clip and its fully frozen row,
+// bits [n, ceil(P/32)] the caller's table
+static inline int run_lin_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,
+                                 const float* A_W, int gt, int gh, int gw, int H, int W, int n, const unsigned* bits,
+                                 float* scores, hipStream_t s) {
+  return run_row_scores(v, b, (long long)n + 1, target, scores, s, [&](long long first, int cnt) {
+    return ivf_lin_stage(x, b, v.C, v.T, H, W, A_H, A_W, gt, gh, gw, n, bits, first, cnt, v.in, v.layout, s);
+  });
+}
+
 // Deletion / insertion curves (curve_ops.hip; an extension): the ncurves * (J + 1) (curve, j) rows of a clip,
 // a rank table per clip; chunks cross clip and curve boundaries
 static inline int run_curve_scores(const Backbone& v, const float* x, int b, const int* target, const float* A_H,

@@ -764,11 +764,19 @@ class _Engine:
         gt, gh, gw, n, seed, anti, AH, AW = self._shap_args(n_perms, grid, sigma, seed, antithetic)
         x = self._clip(x, any_batch=True)
         b = x.shape[0]
-        C, T, H, W = self.clip_shape
         tgt = self._targets(target, b)
         score_x = self._score_x(x, tgt)
         scores = self.shap_scores(x, tgt, n, (gt, gh, gw), sigma, seed, anti)
         cells, stderr, count, total = self.shap_reduce(scores, (gt, gh, gw), seed, anti)
+        amap, frames = self._cell_maps(cells, gt, gh, gw, sigma)
+        return dict(shap_scores=scores, shap_cells=cells, shap_stderr=stderr, shap_count=count, shap_total=total,
+                    score_x=score_x, shap_map=amap, shap_frames=frames)
+
+    def _cell_maps(self, cells, gt, gh, gw, sigma):
+        """(map [b,T,H,W], frames [b,T]) of additive cell values [b,gt,gh,gw] (Shapley, KernelSHAP, LIME): the cells
+        repeated over the frames of their temporal cell and expanded with st_expand; a temporal cell's spatial sum
+        shared equally among its frames, so that the frames sum to the cells"""
+        b, T = cells.shape[0], self.clip_shape[1]
         kt = (torch.arange(T, device=self.device) * gt) // T
         S = cells[:, kt].contiguous()                                   # [b,T,gh,gw]
         share = 1.0 / torch.bincount(kt, minlength=gt).to(torch.float32)[kt]            # 1 / frames of the frame's cell
@@ -777,8 +785,202 @@ class _Engine:
         with torch.cuda.device(self.device):                            # unit rows: the spatial sum per frame
             L.check(L.lib().ivf_stmask_expand_fwd(L.ptr(S), L.ptr(ah), L.ptr(aw), L.ptr(frames), b, T, gh, gw, 1, 1,
                                                   L.stream()))
-        return dict(shap_scores=scores, shap_cells=cells, shap_stderr=stderr, shap_count=count, shap_total=total,
-                    score_x=score_x, shap_map=self.st_expand(S, (gh, gw), sigma), shap_frames=frames * share)
+        return self.st_expand(S, (gh, gw), sigma), frames * share
+
+    # -------------------------------------------------------------- KernelSHAP and LIME (extension)
+    LIN_MAX_PLAYERS, LIN_MAX_ROWS = 1024, 2 ** 20
+
+    def _lin_args(self, n_samples, grid, sigma, seed):
+        """(gt, gh, gw, n, seed, A_H, A_W) of a linear-surrogate call, checked; grid None -> (T, 1, 1): the players are
+        the frames."""
+        if not self._has_st:
+            raise L.IvfError("KernelSHAP and LIME are built for the I3D and CLSTM plans only")
+        gt, gh, gw = self._grid3(grid, (self.clip_shape[1], 1, 1), self.LIN_MAX_PLAYERS)
+        if gt * gh * gw < 2:
+            raise L.IvfError(f"grid {(gt, gh, gw)}: a linear surrogate needs at least 2 cells")
+        try:
+            n, seed = int(n_samples), int(seed)
+        except (TypeError, ValueError):
+            raise L.IvfError(f"n_samples and seed must be integers, got {n_samples!r}, {seed!r}")
+        if not 1 <= n <= self.LIN_MAX_ROWS:
+            raise L.IvfError(f"n_samples must be in [1, 2^20], got {n_samples}")
+        if not 0 <= seed < 2 ** 32:
+            raise L.IvfError(f"seed must be in [0, 2^32), got {seed}")
+        _, _, _, AH, AW = self._st_axes((gh, gw), sigma)
+        return gt, gh, gw, n, seed, AH, AW
+
+    @staticmethod
+    def kshap_size_table(P):
+        """The integer table KernelSHAP's coalition sizes are drawn with, computed here and nowhere else:
+        uint32 [P-2], floor(2^32 CDF(i)) for i = 1 .. P-2, the CDF that of q(s) ~ 1 / (s (P-s)) on 1 .. P-1 (the
+        Shapley kernel summed over the coalitions of a size), by an fp64 cumsum."""
+        s = np.arange(1, P, dtype=np.float64)
+        c = np.cumsum(1.0 / (s * (P - s)))
+        return np.floor(4294967296.0 * (c[:P - 2] / c[-1])).astype(np.uint32)
+
+    @staticmethod
+    def lime_weight_table(P, width=0.25):
+        """fp64 [P+1]: LIME's sample weight by the number m of frozen cells, exp(-D^2 / (2 width^2)) with
+        D = 1 - sqrt((P - m) / P): lime_image's cosine distance to the unperturbed clip under its exponential kernel."""
+        m = np.arange(P + 1, dtype=np.float64)
+        D = 1.0 - np.sqrt((P - m) / P)
+        return np.exp(-(D * D) / (2.0 * width * width))
+
+    def _lin_check_kshap(self, n, P, paired):
+        if n < P - 1:
+            raise L.IvfError(f"KernelSHAP needs n_samples >= P - 1 = {P - 1} rows (got {n}): fewer leave the system singular")
+        if paired and n % 2:
+            raise L.IvfError(f"paired KernelSHAP rows come two by two: n_samples must be even, got {n}")
+
+    def kshap_rows(self, n_samples=256, grid=None, seed=0, paired=True, first=0):
+        """The sampled KernelSHAP rows themselves (ivf_kshap_rows): (bits int32 [n, ceil(P/32)] holding the uint32
+        words -- bit c % 32 of word c / 32 set: the row freezes cell c --, sizes int16 [n]) of rows first ..
+        first + n_samples - 1.  The same for every clip."""
+        gt, gh, gw, n, seed, _, _ = self._lin_args(n_samples, grid, None, seed)
+        P = gt * gh * gw
+        # one spare word: at P = 2 the table is empty and the tensor would have no address
+        table = torch.from_numpy(np.concatenate([self.kshap_size_table(P), np.zeros(1, np.uint32)]).view(np.int32))
+        table = table.to(self.device)
+        bits = torch.empty(n, (P + 31) // 32, dtype=torch.int32, device=self.device)
+        sizes = torch.empty(n, dtype=torch.int16, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().ivf_kshap_rows(seed, int(bool(paired)), int(first), n, gt, gh, gw, L.ptr(table), L.ptr(bits),
+                                           L.ptr(sizes), L.stream()))
+        return bits, sizes
+
+    def lime_rows(self, n_samples=1024, p=0.5, grid=None, seed=0, first=0):
+        """The sampled LIME rows themselves (ivf_lime_rows), packed as kshap_rows packs them: the bits of
+        rise_masks(n_samples, p, grid, seed)."""
+        gt, gh, gw, n, seed, _, _ = self._lin_args(n_samples, grid, None, seed)
+        bits = torch.empty(n, (gt * gh * gw + 31) // 32, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().ivf_lime_rows(seed, rise_thresh(p), int(first), n, gt, gh, gw, L.ptr(bits), L.stream()))
+        return bits
+
+    def _lin_bits(self, bits, P):
+        if not torch.is_tensor(bits) or bits.dtype != torch.int32 or bits.dim() != 2 or \
+                bits.shape[1] != (P + 31) // 32 or bits.shape[0] < 1 or not bits.is_contiguous():
+            raise L.IvfError(f"bits must be a contiguous int32 [n, {(P + 31) // 32}] tensor (kshap_rows, lime_rows), got "
+                             f"{getattr(bits, 'dtype', type(bits))} {tuple(getattr(bits, 'shape', ()))}")
+        L.require_gpu(bits)
+        return bits
+
+    def lin_scores(self, x, target, bits, grid=None, sigma=None):
+        """Scores [b, n+1] of target[clip]: entry [.., k] has the cells of row k of bits frozen per pixel (expanded as
+        st_expand expands a mask), entry [.., n] every cell: ivf_*_lin_scores, forward only, chunks of the plan's
+        max_batch rows; b may exceed max_batch."""
+        if not torch.is_tensor(bits) or bits.dim() != 2:
+            raise L.IvfError("bits must be an int32 [n, ceil(P/32)] tensor (kshap_rows, lime_rows)")
+        gt, gh, gw, n, _, AH, AW = self._lin_args(bits.shape[0], grid, sigma, 0)
+        bits = self._lin_bits(bits, gt * gh * gw)
+        x = self._clip(x, any_batch=True)
+        b = x.shape[0]
+        tgt = self._targets(target, b)
+        scores = torch.empty(b, n + 1, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(self._fn("lin_scores")(self._h, L.ptr(x), b, L.ptr(tgt), L.ptr(AH), L.ptr(AW), gt, gh, gw, n,
+                                           L.ptr(bits), L.ptr(scores), L.stream()))
+        return scores
+
+    LIN_KINDS = {"kernelshap": 0, "lime": 1}
+
+    def lin_solve(self, kind, scores, score_x, bits, P, wtab=None, ridge=0.0):
+        """The fit of scores [b,n+1] and score_x [b] on the rows `bits` of P players, fp64 on the device
+        (ivf_lin_moments -> ivf_lin_solve -> ivf_lin_fit): kind 'kernelshap' (unit weights, the efficiency constraint
+        solved exactly) or 'lime' (wtab [P+1] fp64 by the number of frozen cells, ridge, a free intercept).  Returns a
+        dict of device tensors: cells [b,P], intercept [b], total [b] (score_x - the fully frozen row's score), ok
+        (int32 [b]: 0 where a score of the clip is not finite, and everywhere where the system is singular; then the
+        clip's cells, intercept and r2 are NaN) and r2 [b]."""
+        if kind not in self.LIN_KINDS:
+            raise L.IvfError(f"kind must be one of {', '.join(repr(k) for k in self.LIN_KINDS)}, got {kind!r}")
+        P = int(P)
+        if not 1 <= P <= self.LIN_MAX_PLAYERS:
+            raise L.IvfError(f"need 1 <= P <= {self.LIN_MAX_PLAYERS} players, got {P}")
+        bits = self._lin_bits(bits, P)
+        n = bits.shape[0]
+        s = L.f32c(scores)
+        L.require_gpu(s)
+        if s.dim() != 2 or s.shape[1] != n + 1:
+            raise L.IvfError(f"scores must be [b, {n + 1}] (the {n} rows and the fully frozen one), got {tuple(s.shape)}")
+        b = s.shape[0]
+        sx = L.f32c(score_x.reshape(b))
+        dev = s.device
+        wt = None
+        if wtab is not None:
+            wt = torch.as_tensor(np.ascontiguousarray(np.asarray(wtab, np.float64).reshape(-1))).to(dev)
+            if wt.numel() != P + 1:
+                raise L.IvfError(f"wtab must hold P + 1 = {P + 1} weights, got {wt.numel()}")
+        f64 = dict(dtype=torch.float64, device=dev)
+        N, v, Wsum = torch.empty(P, P, **f64), torch.empty(P, **f64), torch.empty(1, **f64)
+        r, t, wrow = torch.empty(b, P, **f64), torch.empty(b, **f64), torch.empty(n, **f64)
+        ok = torch.empty(b, dtype=torch.int32, device=dev)
+        cells, icpt, total, r2 = (torch.empty(b, P, device=dev), torch.empty(b, device=dev), torch.empty(b, device=dev),
+                                  torch.empty(b, device=dev))
+        work = _arena(L.lib().ivf_lin_workspace_bytes(P), dev)
+        with torch.cuda.device(dev):
+            L.check(L.lib().ivf_lin_moments(L.ptr(s), L.ptr(sx), L.ptr(bits), L.ptr(wt), b, n, P, L.ptr(N), L.ptr(v),
+                                            L.ptr(Wsum), L.ptr(r), L.ptr(t), L.ptr(wrow), L.ptr(ok), L.stream()))
+            L.check(L.lib().ivf_lin_solve(self.LIN_KINDS[kind], L.ptr(N), L.ptr(v), L.ptr(Wsum), L.ptr(r), L.ptr(t),
+                                          L.ptr(s), L.ptr(sx), b, n, P, float(ridge), L.ptr(work), L.ptr(cells),
+                                          L.ptr(icpt), L.ptr(total), L.ptr(ok), L.stream()))
+            L.check(L.lib().ivf_lin_fit(L.ptr(s), L.ptr(sx), L.ptr(bits), L.ptr(wrow), L.ptr(cells), L.ptr(icpt), L.ptr(t),
+                                        L.ptr(Wsum), L.ptr(ok), b, n, P, L.ptr(r2), L.stream()))
+        return dict(cells=cells, intercept=icpt, total=total, ok=ok, r2=r2)
+
+    def kernelshap(self, x, target, n_samples=256, grid=None, sigma=None, seed=0, paired=True):
+        """KernelSHAP (Lundberg & Lee 2017) of the cells of grid = (gt, gh, gw) (default (T, 1, 1): the frames) under
+        the per-pixel freeze, for target[clip] on b clips, b may exceed max_batch: n_samples coalitions whose sizes
+        follow the Shapley kernel (paired: every odd row is the complement of the one before it), one forward each and
+        one for the fully frozen clip, then the least-squares fit of the score drops under the efficiency constraint,
+        in fp64 on the device.  A cell's value is > 0 where freezing it lowers the score.  Returns a dict of device
+        tensors: kshap_scores [b,n+1], kshap_cells [b,gt,gh,gw], kshap_total [b] (= score_x - score(fully frozen
+        clip), what the cells sum to), kshap_ok (int32 [b]; 0: a score was not finite or the sampled system is singular,
+        the cells are NaN), kshap_r2 [b], kshap_sizes (int16 [n]), score_x [b], kshap_map [b,T,H,W] and kshap_frames
+        [b,T] (built from the cells as shapley() builds its own)."""
+        gt, gh, gw, n, seed, AH, AW = self._lin_args(n_samples, grid, sigma, seed)
+        P = gt * gh * gw
+        self._lin_check_kshap(n, P, paired)
+        x = self._clip(x, any_batch=True)
+        b = x.shape[0]
+        tgt = self._targets(target, b)
+        score_x = self._score_x(x, tgt)
+        bits, sizes = self.kshap_rows(n, (gt, gh, gw), seed, paired)
+        scores = self.lin_scores(x, tgt, bits, (gt, gh, gw), sigma)
+        fit = self.lin_solve("kernelshap", scores, score_x, bits, P)
+        cells = fit["cells"].reshape(b, gt, gh, gw)
+        amap, frames = self._cell_maps(cells, gt, gh, gw, sigma)
+        return dict(kshap_scores=scores, kshap_cells=cells, kshap_total=fit["total"], kshap_ok=fit["ok"],
+                    kshap_r2=fit["r2"], kshap_sizes=sizes, score_x=score_x, kshap_map=amap, kshap_frames=frames)
+
+    def lime(self, x, target, n_samples=1024, p=0.5, grid=None, sigma=None, seed=0, width=0.25, ridge=1.0):
+        """LIME (Ribeiro et al. 2016) of the cells of grid = (gt, gh, gw) (default (T, 1, 1): the frames) under the
+        per-pixel freeze, for target[clip] on b clips, b may exceed max_batch: n_samples Bernoulli(p) rows (RISE's
+        masks), one forward each, then the ridge regression of the score drops on the frozen cells with a free
+        intercept, every row weighted by exp(-D^2 / (2 width^2)) of its distance D to the clip, in fp64 on the device.
+        Returns a dict of device tensors: lime_scores [b,n+1] (entry n: the fully frozen clip, not part of the fit),
+        lime_cells [b,gt,gh,gw], lime_intercept [b], lime_ok (int32 [b]), lime_r2 [b], score_x [b], lime_map [b,T,H,W]
+        and lime_frames [b,T]."""
+        gt, gh, gw, n, seed, AH, AW = self._lin_args(n_samples, grid, sigma, seed)
+        P = gt * gh * gw
+        try:
+            width, ridge = float(width), float(ridge)
+        except (TypeError, ValueError):
+            raise L.IvfError(f"width and ridge must be numbers, got {width!r}, {ridge!r}")
+        if not (width > 0.0 and math.isfinite(width)):
+            raise L.IvfError(f"width must be a finite number > 0, got {width}")
+        if not (ridge >= 0.0 and math.isfinite(ridge)):
+            raise L.IvfError(f"ridge must be a finite number >= 0, got {ridge}")
+        x = self._clip(x, any_batch=True)
+        b = x.shape[0]
+        tgt = self._targets(target, b)
+        score_x = self._score_x(x, tgt)
+        bits = self.lime_rows(n, p, (gt, gh, gw), seed)
+        scores = self.lin_scores(x, tgt, bits, (gt, gh, gw), sigma)
+        fit = self.lin_solve("lime", scores, score_x, bits, P, self.lime_weight_table(P, width), ridge)
+        cells = fit["cells"].reshape(b, gt, gh, gw)
+        amap, frames = self._cell_maps(cells, gt, gh, gw, sigma)
+        return dict(lime_scores=scores, lime_cells=cells, lime_intercept=fit["intercept"], lime_ok=fit["ok"],
+                    lime_r2=fit["r2"], score_x=score_x, lime_map=amap, lime_frames=frames)
 
     # -------------------------------------------------------------- deletion / insertion curves (extension, DESIGN 17)
     def _curve_args(self, grid, sigma, step=1, curves=3, order=0):
@@ -1281,8 +1483,8 @@ class TFCLSTMEngine(_Engine):
     (mask/find_mask_kth.py:300-452, mask/gradcam.py:28-111) on libivf_hip's generic direct-convolution kernels
     (csrc/tf_clstm.hip).  Clips are NCTHW like everywhere else; `from_tf_layout` converts [B,T,H,W,C].
     The plan perturbs by freezing only and has no one-blob entry (the inherited `blob_scores` finds no symbol); `ig`,
-    `ig_path_scores`, the `rise*`, `shap*` and `curve*` entries, `faithfulness`, `smoothgrad` and `sg_noise` refuse with
-    IvfError."""
+    `ig_path_scores`, the `rise*`, `shap*` and `curve*` entries, `faithfulness`, `smoothgrad`, `sg_noise`, `kernelshap`,
+    `lime` and their row entries refuse with IvfError."""
     _prefix = "tfclstm"
     _has_mode = False
     _has_st = False

@@ -52,8 +52,21 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                     sg_level=0.15, sg_seed=0, do_shapley=False, shap_perms=64, shap_grid=None, shap_sigma=None,
                     shap_seed=0, do_curves=False, curve_grid=None, curve_sigma=None, curve_step=1, cam_kinds=(),
                     cam_target=None, do_scorecam=False, scorecam_target=None, scorecam_weights="increase",
-                    scorecam_perturb="freeze", scorecam_sigma=None, scorecam_channels=None):
-    """do_scorecam (the drivers' doScoreCam, an extension: DESIGN 19) also runs Score-CAM of the target's score on
+                    scorecam_perturb="freeze", scorecam_sigma=None, scorecam_channels=None, do_kernelshap=False,
+                    kshap_samples=256, kshap_grid=None, kshap_sigma=None, kshap_seed=0, do_lime=False, lime_samples=1024,
+                    lime_p=0.5, lime_grid=None, lime_sigma=None, lime_seed=0, lime_width=0.25, lime_ridge=1.0):
+    """do_kernelshap, do_lime (the drivers' doKernelShap and doLime, extensions: DESIGN 20) also fit a linear surrogate
+    of the target's score drop in the frozen cells of kshap_grid / lime_grid (gt, gh, gw) (default (T, 1, 1): the
+    frames; blurred by kshap_sigma / lime_sigma input pixels; forward passes only, the fit in fp64 on the device):
+    KernelSHAP on kshap_samples paired coalitions drawn from kshap_seed, LIME on lime_samples Bernoulli(lime_p) rows
+    drawn from lime_seed with kernel width lime_width and ridge lime_ridge.  Each writes a further list of records --
+    true_class, pred_class, video_id, KshapHeatMap [T,H,W], KshapCells [gt,gh,gw], KshapFrames [T], kshap_total,
+    kshap_ok, kshap_r2, n_samples, seed; and LimeHeatMap, LimeCells, LimeFrames, lime_intercept, lime_ok, lime_r2,
+    n_samples, seed -- to a pickle named like the Grad-CAM one with KernelShap / Lime in place of GradCam; with the
+    strips on, a further set of heat-map strips (folders `kernelshap` and `lime` beside `combined`) blends max(map, 0)
+    normalised per frame, as Shapley's; the plan holds at least blob_batch clips so that the rows of a loader batch fill
+    it; do_curves ranks the maps under 'kshap' and 'lime'.  Off, nothing changes.
+    do_scorecam (the drivers' doScoreCam, an extension: DESIGN 19) also runs Score-CAM of the target's score on
     scorecam_target (default: the Grad-CAM target; scorecam_channels = (first, count) a window of its channels, each
     normalised, expanded with a blur of scorecam_sigma input pixels and applied as scorecam_perturb 'freeze' or 'blank',
     weighted as scorecam_weights 'increase' or 'softmax'; forward passes only) and writes a further list of records --
@@ -119,6 +132,7 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
     flt = _class_filter(classOI)
     masks, time_results, cam_results, ig_results, rise_results, sg_results = [], [], [], [], [], []
     shap_results, curve_results, fam_results, scorecam_results = [], [], [], []
+    kshap_results, lime_results = [], []
     cam_kinds = tuple(cam_kinds) if doGradCam else ()
     if write_files and not os.path.exists(results_path):
         os.makedirs(results_path)
@@ -138,7 +152,7 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
             continue
         xs = x[keep].contiguous()
         eng = net._engine_for(xs, min_batch=blob_batch) if mask_mode in ("combi", "stcombi") or do_rise or do_smoothgrad \
-            or do_shapley or do_curves or do_scorecam else net._engine_for(xs)
+            or do_shapley or do_curves or do_scorecam or do_kernelshap or do_lime else net._engine_for(xs)
         search = ivf_search.MaskSearch(eng, lam1, lam2, N, temporalMaskType, threshold=0.9, lr=0.2,
                                        grad_cam_type=hyper_params.get("gradCamType", "guessed"),
                                        do_gradcam=doGradCam, run_temp_mask=runTempMask,
@@ -154,11 +168,15 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                        cam_kinds=cam_kinds, cam_target=cam_target, do_scorecam=do_scorecam,
                                        scorecam_target=scorecam_target, scorecam_weights=scorecam_weights,
                                        scorecam_perturb=scorecam_perturb, scorecam_sigma=scorecam_sigma,
-                                       scorecam_channels=scorecam_channels)
+                                       scorecam_channels=scorecam_channels, do_kernelshap=do_kernelshap,
+                                       kshap_samples=kshap_samples, kshap_grid=kshap_grid, kshap_sigma=kshap_sigma,
+                                       kshap_seed=kshap_seed, do_lime=do_lime, lime_samples=lime_samples, lime_p=lime_p,
+                                       lime_grid=lime_grid, lime_sigma=lime_sigma, lime_seed=lime_seed,
+                                       lime_width=lime_width, lime_ridge=lime_ridge)
         res = search.run(xs, labels[keep])
         host = {k: v.detach().cpu() for k, v in res.items()
                 if k not in ("gradcam", "box_scores", "ig_map", "rise_map", "sg_map", "sg_sq_map", "sg_var_map", "shap_map",
-                            "scorecam_map")}
+                            "scorecam_map", "kshap_map", "lime_map")}
         spacetime = runTempMask and mask_mode in ("spacetime", "stcombi")
         st_maps = eng.st_expand(res["st_mask"], search.st_grid(xs), mask_sigma) if spacetime and write_files and visualise \
             else None
@@ -199,6 +217,17 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                 pos = res["shap_map"].clamp_min(0.0)
                 top = pos.amax(dim=(2, 3), keepdim=True)
                 shap_heat = torch.where(top > 0, pos / torch.where(top > 0, top, torch.ones_like(top)), torch.zeros_like(pos))
+        lin_heat = {}
+        for on, name in ((do_kernelshap, "kshap"), (do_lime, "lime")):
+            if on:
+                host[name + "_map"] = res[name + "_map"].detach().cpu()
+                if runTempMask and write_files and visualise:
+                    # as shap_heat: max(map, 0) scaled to [0,1] per frame; a frame without a positive value (and a map
+                    # that is NaN because its fit was refused) stays all zero
+                    pos = torch.nan_to_num(res[name + "_map"], nan=0.0).clamp_min(0.0)
+                    top = pos.amax(dim=(2, 3), keepdim=True)
+                    lin_heat[name] = torch.where(top > 0, pos / torch.where(top > 0, top, torch.ones_like(top)),
+                                                 torch.zeros_like(pos))
         scorecam_heat = None
         if do_scorecam:
             host["scorecam_map"] = res["scorecam_map"].detach().cpu()
@@ -281,6 +310,24 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                                      'ShapFrames': host["shap_frames"][j].numpy().astype(np.float32),
                                      'shap_total': float(host["shap_total"][j]),
                                      'n_perms': int(shap_perms), 'seed': int(shap_seed)})
+            if do_kernelshap:
+                kshap_results.append({'true_class': true_class, 'pred_class': pred,
+                                      'video_id': int(vid) if flavour == "smth" else vid,
+                                      'KshapHeatMap': host["kshap_map"][j].numpy().astype(np.float32),
+                                      'KshapCells': host["kshap_cells"][j].numpy().astype(np.float32),
+                                      'KshapFrames': host["kshap_frames"][j].numpy().astype(np.float32),
+                                      'kshap_total': float(host["kshap_total"][j]), 'kshap_ok': int(host["kshap_ok"][j]),
+                                      'kshap_r2': float(host["kshap_r2"][j]),
+                                      'n_samples': int(kshap_samples), 'seed': int(kshap_seed)})
+            if do_lime:
+                lime_results.append({'true_class': true_class, 'pred_class': pred,
+                                     'video_id': int(vid) if flavour == "smth" else vid,
+                                     'LimeHeatMap': host["lime_map"][j].numpy().astype(np.float32),
+                                     'LimeCells': host["lime_cells"][j].numpy().astype(np.float32),
+                                     'LimeFrames': host["lime_frames"][j].numpy().astype(np.float32),
+                                     'lime_intercept': float(host["lime_intercept"][j]), 'lime_ok': int(host["lime_ok"][j]),
+                                     'lime_r2': float(host["lime_r2"][j]),
+                                     'n_samples': int(lime_samples), 'seed': int(lime_seed)})
             if do_scorecam:
                 scorecam_results.append({'true_class': true_class, 'pred_class': pred,
                                          'video_id': int(vid) if flavour == "smth" else vid,
@@ -330,6 +377,12 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
                     for kind in ("freeze", "reverse"):
                         viz.create_image_arrays(xs, shap_heat[j], tmask, j, kind, os.path.join(os.path.dirname(d), "shapley"),
                                                 str(vid), 0, xs.shape[4], xs.shape[3])
+                for name, folder in (("kshap", "kernelshap"), ("lime", "lime")):
+                    if name in lin_heat:
+                        for kind in ("freeze", "reverse"):
+                            viz.create_image_arrays(xs, lin_heat[name][j], tmask, j, kind,
+                                                    os.path.join(os.path.dirname(d), folder), str(vid), 0, xs.shape[4],
+                                                    xs.shape[3])
                 if scorecam_heat is not None:
                     for kind in ("freeze", "reverse"):
                         viz.create_image_arrays(xs, scorecam_heat[j], tmask, j, kind,
@@ -369,6 +422,12 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
         if do_shapley:
             with open(os.path.join(results_path, gname.replace("GradCam", "Shapley").replace(os.sep, "_")), "wb") as f:
                 pickle.dump(shap_results, f)
+        if do_kernelshap:
+            with open(os.path.join(results_path, gname.replace("GradCam", "KernelShap").replace(os.sep, "_")), "wb") as f:
+                pickle.dump(kshap_results, f)
+        if do_lime:
+            with open(os.path.join(results_path, gname.replace("GradCam", "Lime").replace(os.sep, "_")), "wb") as f:
+                pickle.dump(lime_results, f)
         if do_scorecam:
             with open(os.path.join(results_path, gname.replace("GradCam", "ScoreCam").replace(os.sep, "_")), "wb") as f:
                 pickle.dump(scorecam_results, f)
@@ -380,6 +439,8 @@ def find_masks_impl(dat_loader, model, hyper_params, lam1, lam2, N, temporalMask
     find_masks_impl.last_rise_results = rise_results
     find_masks_impl.last_sg_results = sg_results
     find_masks_impl.last_shap_results = shap_results
+    find_masks_impl.last_kshap_results = kshap_results
+    find_masks_impl.last_lime_results = lime_results
     find_masks_impl.last_curve_results = curve_results
     find_masks_impl.last_cam_family_results = fam_results
     find_masks_impl.last_scorecam_results = scorecam_results

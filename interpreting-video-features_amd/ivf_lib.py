@@ -116,6 +116,14 @@ _SIGS = {
     "ivf_curve_ranks": (c_int, [_P] + [_I] * 7 + [_P, _P]),
     "ivf_curve_stage": (c_int, [_P] + [_I] * 5 + [_P, _P] + [_I] * 3 + [_P, _I, _I, ctypes.c_longlong, _I, _P, _I, _P]),
     "ivf_curve_reduce": (c_int, [_P] + [_I] * 5 + [_P] * 3),
+    # csrc/linsur_ops.hip (KernelSHAP and LIME, documented extension)
+    "ivf_kshap_rows": (c_int, [_U] + [_I] * 6 + [_P] * 4),
+    "ivf_lime_rows": (c_int, [_U, _U] + [_I] * 5 + [_P, _P]),
+    "ivf_lin_stage": (c_int, [_P] + [_I] * 5 + [_P, _P] + [_I] * 4 + [_P, ctypes.c_longlong, _I, _P, _I, _P]),
+    "ivf_lin_moments": (c_int, [_P] * 4 + [_I] * 3 + [_P] * 8),
+    "ivf_lin_workspace_bytes": (c_size_t, [_I]),
+    "ivf_lin_solve": (c_int, [_I] + [_P] * 7 + [_I] * 3 + [ctypes.c_double] + [_P] * 6),
+    "ivf_lin_fit": (c_int, [_P] * 9 + [_I] * 3 + [_P, _P]),
     # csrc/scorecam_ops.hip (Score-CAM, documented extension)
     "ivf_scorecam_normalise": (c_int, [_P, _I, _I, _I] + [_P] * 5),
     "ivf_scorecam_stage": (c_int, [_P] + [_I] * 5 + [_P, _P] + [_I] * 3 + [_P, _I, _I, ctypes.c_longlong, _I, _P, _I, _P]),
@@ -182,6 +190,7 @@ _SIGS = {
     "ivf_i3d_box_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 5 + [_P, _P]),
     "ivf_i3d_rise_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_U, _U, _P, _P]),
     "ivf_i3d_shap_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_P, _P, _P]),
+    "ivf_i3d_lin_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_P, _P, _P]),
     "ivf_i3d_curve_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 3 + [_P, _I, _I, _P, _P]),
     "ivf_i3d_scorecam_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 3 + [_P, _I, _I, _P, _P]),
     "ivf_i3d_smoothgrad": (c_int, [_P, _P, _I, _P, _I, _F, _U] + [_P] * 10),
@@ -227,6 +236,7 @@ _SIGS = {
     "ivf_clstm_box_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 5 + [_P, _P]),
     "ivf_clstm_rise_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_U, _U, _P, _P]),
     "ivf_clstm_shap_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_P, _P, _P]),
+    "ivf_clstm_lin_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 4 + [_P, _P, _P]),
     "ivf_clstm_curve_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 3 + [_P, _I, _I, _P, _P]),
     "ivf_clstm_scorecam_scores": (c_int, [_P, _P, _I, _P, _P, _P] + [_I] * 3 + [_P, _I, _I, _P, _P]),
     "ivf_clstm_smoothgrad": (c_int, [_P, _P, _I, _P, _I, _F, _U] + [_P] * 10),

@@ -247,8 +247,20 @@ class MaskSearch:
                  rise_seed=0, do_smoothgrad=False, sg_samples=32, sg_level=0.15, sg_seed=0, do_shapley=False,
                  shap_perms=64, shap_grid=None, shap_sigma=None, shap_seed=0, do_curves=False, curve_grid=None,
                  curve_sigma=None, curve_step=1, cam_kinds=(), cam_target=None, do_scorecam=False, scorecam_target=None,
-                 scorecam_weights="increase", scorecam_perturb="freeze", scorecam_sigma=None, scorecam_channels=None):
-        """do_scorecam (an extension without a counterpart in the reference): also run Score-CAM of the
+                 scorecam_weights="increase", scorecam_perturb="freeze", scorecam_sigma=None, scorecam_channels=None,
+                 do_kernelshap=False, kshap_samples=256, kshap_grid=None, kshap_sigma=None, kshap_seed=0, do_lime=False,
+                 lime_samples=1024, lime_p=0.5, lime_grid=None, lime_sigma=None, lime_seed=0, lime_width=0.25,
+                 lime_ridge=1.0):
+        """do_kernelshap, do_lime (extensions without a counterpart in the reference): also fit a linear
+        surrogate of the target's score drop in the frozen cells of kshap_grid / lime_grid (gt, gh, gw) (default
+        (T, 1, 1): the frames), blurred by kshap_sigma / lime_sigma input pixels, forward passes only, the fit in fp64 on
+        the device.  KernelSHAP: kshap_samples paired coalitions with Shapley-kernel sizes drawn from kshap_seed, the
+        efficiency constraint solved exactly; run() then also returns kshap_map [b,T,H,W], kshap_cells [b,gt,gh,gw],
+        kshap_frames [b,T], kshap_total, kshap_ok and kshap_r2 [b].  LIME: lime_samples Bernoulli(lime_p) rows drawn
+        from lime_seed, weighted by an exponential kernel of width lime_width, ridge lime_ridge, a free intercept; run()
+        then also returns lime_map, lime_cells, lime_frames, lime_intercept, lime_ok and lime_r2.  do_curves ranks the
+        maps under 'kshap' and 'lime'.  The perturbation is the per-pixel freeze only.
+        do_scorecam (an extension without a counterpart in the reference): also run Score-CAM of the
         target's score on scorecam_target (an endpoint name, or the ConvLSTM engine's layer; default: the Grad-CAM
         target) -- every channel (or the window scorecam_channels = (first, count)) normalised, expanded to the clip
         (blurred by scorecam_sigma input pixels) and applied as scorecam_perturb ('freeze' or 'blank'), weighted as
@@ -327,6 +339,14 @@ class MaskSearch:
         self.shap_perms, self.shap_grid, self.shap_sigma, self.shap_seed = shap_perms, shap_grid, shap_sigma, shap_seed
         if self.do_shapley and mask_type != "freeze":
             raise L.IvfError("Shapley value sampling perturbs by freezing only")
+        self.do_kernelshap, self.do_lime = bool(do_kernelshap), bool(do_lime)                         # read only when on
+        self.kshap_samples, self.kshap_grid, self.kshap_sigma, self.kshap_seed = kshap_samples, kshap_grid, kshap_sigma, kshap_seed
+        self.lime_samples, self.lime_p, self.lime_grid, self.lime_sigma = lime_samples, lime_p, lime_grid, lime_sigma
+        self.lime_seed, self.lime_width, self.lime_ridge = lime_seed, lime_width, lime_ridge
+        if self.do_kernelshap and mask_type != "freeze":
+            raise L.IvfError("KernelSHAP perturbs by freezing only")
+        if self.do_lime and mask_type != "freeze":
+            raise L.IvfError("LIME perturbs by freezing only")
         self.do_curves = bool(do_curves)                                                              # read only when on
         self.curve_grid, self.curve_sigma, self.curve_step = curve_grid, curve_sigma, curve_step
         if self.do_curves and mask_type != "freeze":
@@ -416,6 +436,16 @@ class MaskSearch:
                             seed=self.shap_seed)
             for k in ("shap_map", "shap_cells", "shap_stderr", "shap_count", "shap_frames", "shap_total"):
                 out[k] = r[k]
+        if self.do_kernelshap:
+            ks = eng.kernelshap(x, target, n_samples=self.kshap_samples, grid=self.kshap_grid, sigma=self.kshap_sigma,
+                                seed=self.kshap_seed)
+            for k in ("kshap_map", "kshap_cells", "kshap_frames", "kshap_total", "kshap_ok", "kshap_r2"):
+                out[k] = ks[k]
+        if self.do_lime:
+            lm = eng.lime(x, target, n_samples=self.lime_samples, p=self.lime_p, grid=self.lime_grid, sigma=self.lime_sigma,
+                          seed=self.lime_seed, width=self.lime_width, ridge=self.lime_ridge)
+            for k in ("lime_map", "lime_cells", "lime_frames", "lime_intercept", "lime_ok", "lime_r2"):
+                out[k] = lm[k]
         if self.do_curves:
             self._run_curves(x, target, out, r["shap_scores"] if self.do_shapley else None)
         return out
@@ -428,7 +458,8 @@ class MaskSearch:
             if "st_mask" in out:
                 attrs["st_mask"] = self.engine.st_expand(out["st_mask"], self.st_grid(x), self.mask_sigma)
             for name, key in [("gradcam", "gradcam"), ("ig", "ig_map"), ("rise", "rise_map"), ("sg", "sg_map"),
-                              ("shap", "shap_map"), ("scorecam", "scorecam_map")] + [(k, "cam_" + k) for k in self.cam_kinds]:
+                              ("shap", "shap_map"), ("scorecam", "scorecam_map"), ("kshap", "kshap_map"),
+                              ("lime", "lime_map")] + [(k, "cam_" + k) for k in self.cam_kinds]:
                 if key in out and tuple(out[key].shape[1:]) == (T,) + HW:
                     attrs[name] = out[key]
             return attrs
@@ -441,7 +472,8 @@ class MaskSearch:
                 attrs[k] = out["cam_" + k].float().mean(dim=(2, 3))
         if "scorecam_map" in out and out["scorecam_map"].shape[1] == T:
             attrs["scorecam"] = out["scorecam_map"].float().mean(dim=(2, 3))
-        for name, key in (("ig", "ig_frames"), ("rise", "rise_frames"), ("sg", "sg_frames"), ("shap", "shap_frames")):
+        for name, key in (("ig", "ig_frames"), ("rise", "rise_frames"), ("sg", "sg_frames"), ("shap", "shap_frames"),
+                          ("kshap", "kshap_frames"), ("lime", "lime_frames")):
             if key in out:
                 attrs[name] = out[key]
         return attrs
