@@ -142,11 +142,14 @@ __host__ __device__ constexpr int halo_plane_rows(int HH, int HW) {
 // AM = operand mode (conv_common.h): NPA activation planes and NPB weight planes sit in LDS, the tap loop issues the
 // mode's MFMA sequence per 16-deep k-step (3 / 2 / 6 passes); AM_BF16 stages bf16 activations as they are and its
 // epilogue stores bf16 (the depth-to-space forms always write fp32: the stem's input gradient).
-template <int AM, int TT, int BN, int WROWS, int WCOLS, int KS, int BKH, int TH, int TW, int TPS, bool DMA>
+// SL = short boxes last: the tile decode below for launches with short edge boxes (halo_short_edges != 0); every other
+// launch runs the SL = false kernel, whose decode is the plain box order and which never reads short_edges.
+template <int AM, int TT, int BN, int WROWS, int WCOLS, int KS, int BKH, int TH, int TW, int TPS, bool DMA, bool SL>
 __global__ __launch_bounds__((TT * TH * TW / WROWS) * (BN / WCOLS) * KS * 64) void conv3d_halo_kernel(ConvKArgs a,
                                                                                                 int tilesT,
                                                                                                 int tilesH,
-                                                                                                int tilesW) {
+                                                                                                int tilesW,
+                                                                                                int short_edges) {
   constexpr int BM = TT * TH * TW;
   constexpr int NPA = OpPlanes<AM>::A, NPB = OpPlanes<AM>::B;
   static_assert(BM % WROWS == 0 && WROWS % 32 == 0 && BN % WCOLS == 0 && WCOLS % 32 == 0, "tile");
@@ -187,10 +190,43 @@ __global__ __launch_bounds__((TT * TH * TW / WROWS) * (BN / WCOLS) * KS * 64) vo
   int tile = xcd_remap(blockIdx.x, gridDim.x);
   const int nt = tile % a.ntiles;
   tile /= a.ntiles;
-  const int tw = tile % tilesW;
-  tile /= tilesW;
-  const int th = tile % tilesH;
-  tile /= tilesH;
+  int tw, th;
+  if constexpr (SL) {
+    // Short boxes last (halo_short_edges: the narrow last box column, a last box row half live or less).  A short box
+    // takes about half to two thirds of a full box's time and the wide tiles run one workgroup per CU, a few rounds of
+    // them per launch (32 clips on a 28 x 28 map: 1024 boxes, 4 per CU, 7 of every 16 short).  Dealt in box order the
+    // short ones leave the CUs uneven when the launch ends; dealt after the full ones they fill its last round
+    // (profiles/halo_edge_order.txt).  "Last" is per XCD: xcd_remap hands each XCD one contiguous eighth of the grid,
+    // so the order is made inside each eighth, ppc = planes / 8 planes (clips x t-boxes) each.  The launch asks for
+    // this order only when the planes divide into eighths: over the whole grid it would give the low XCDs all the
+    // full boxes and the high ones all the short ones.  Which workgroup computes a box changes nothing in the box.
+    static_assert(TT == 4 && TW == 8, "short boxes exist in the 4 x TH x 8 tiles only");
+    const int CI = tilesW - (short_edges & 1), RI = tilesH - (short_edges >> 1);
+    const int ppc = (a.B * tilesT) >> 3;
+    const int range = tile / (ppc * tilesH * tilesW);
+    int r = tile - range * (ppc * tilesH * tilesW), pl;
+    th = tilesH - 1, tw = tilesW - 1;
+    if (r < ppc * RI * CI) {                                     // full boxes: w, h, plane
+      tw = r % CI;
+      r /= CI;
+      th = r % RI;
+      pl = r / RI;
+    } else if ((r -= ppc * RI * CI) < ppc * RI * (tilesW - CI)) {   // last column above the corner
+      th = r % RI;
+      pl = r / RI;
+    } else if ((r -= ppc * RI * (tilesW - CI)) < ppc * CI * (tilesH - RI)) {   // last row left of the corner
+      tw = r % CI;
+      pl = r / CI;
+    } else {                                                     // the corner
+      pl = r - ppc * CI * (tilesH - RI);
+    }
+    tile = range * ppc + pl;
+  } else {
+    tw = tile % tilesW;
+    tile /= tilesW;
+    th = tile % tilesH;
+    tile /= tilesH;
+  }
   const int tt = tile % tilesT;
   const int b = tile / tilesT;
   const int t0 = tt * TT, h0 = th * TH, w0 = tw * TW;
@@ -744,6 +780,17 @@ constexpr size_t halo_lds_bytes(int NPA, int NPB, int kT, int kH, int kW, bool d
   return shm;
 }
 
+// Which edges of the box grid hold short boxes, which the SL kernel deals last: bit 0 = the last box column is narrow
+// (4 x TH x 8 boxes whose map ends within their first 4 columns: half the MFMA tiles, narrow_box_pos), bit 1 = the
+// last box row is half live or less.  A grid of a single column or row has no "last"; and the order is made per
+// eighth of the grid (see the kernel), so a launch whose planes do not divide by 8 keeps the box order.
+static int halo_short_edges(const HaloTile& t, const ConvKArgs& a, int tilesT, int tilesH, int tilesW) {
+  if (t.TT != 4 || t.TW != 8 || a.d2s || (a.B * tilesT) % 8) return 0;
+  const int narrow = tilesW > 1 && a.Wo - (tilesW - 1) * t.TW <= 4;
+  const int low = tilesH > 1 && 2 * (a.Ho - (tilesH - 1) * t.TH) <= t.TH;
+  return narrow | (low << 1);
+}
+
 // A tile is built for an operand mode only if its LDS footprint fits for the 3x3x3 case (the 6-pass mode holds three
 // activation planes: mostly the 16-channel-chunk tiles remain); anything else reports IVF_ERR_UNSUPPORTED.
 template <int AM, int V>
@@ -753,22 +800,27 @@ static int launch_halo(ConvKArgs& a, hipStream_t s) {
     set_error("conv3d_halo: variant %d needs more than 160 KB of LDS in this arithmetic mode", V);
     return IVF_ERR_UNSUPPORTED;
   } else {
-    constexpr auto kernel = &conv3d_halo_kernel<AM, t.TT, t.BN, t.WROWS, t.WCOLS, t.KS, t.BKH, t.TH, t.TW, t.TPS, t.DMA>;
     constexpr int NT = (t.TT * t.TH * t.TW / t.WROWS) * (t.BN / t.WCOLS) * t.KS * 64;
     const size_t shm = halo_lds_bytes<V>(OpPlanes<AM>::A, OpPlanes<AM>::B, a.kT, a.kH, a.kW, a.d2s);
     if (shm > HALO_LDS_MAX) {
       set_error("conv3d_halo: %zu bytes of LDS needed", shm);
       return IVF_ERR_UNSUPPORTED;
     }
-    static LdsAttrOnce once;
-    IVF_PROPAGATE(raise_lds_limit(reinterpret_cast<const void*>(kernel), HALO_LDS_MAX, once));
     const int tilesT = cdiv(a.To, t.TT), tilesH = cdiv(a.Ho, t.TH), tilesW = cdiv(a.Wo, t.TW);
+    // two kernels per 4 x TH x 8 tile: the box order, and short boxes last for launches that have short boxes
+    const int short_edges = halo_short_edges(t, a, tilesT, tilesH, tilesW);
+    auto kernel = &conv3d_halo_kernel<AM, t.TT, t.BN, t.WROWS, t.WCOLS, t.KS, t.BKH, t.TH, t.TW, t.TPS, t.DMA, false>;
+    static LdsAttrOnce once[2];
+    if constexpr (t.TT == 4 && t.TW == 8) {
+      if (short_edges) kernel = &conv3d_halo_kernel<AM, t.TT, t.BN, t.WROWS, t.WCOLS, t.KS, t.BKH, t.TH, t.TW, t.TPS, t.DMA, true>;
+    }
+    IVF_PROPAGATE(raise_lds_limit(reinterpret_cast<const void*>(kernel), HALO_LDS_MAX, once[short_edges != 0]));
     a.ntiles = cdiv(a.Cout, t.BN);
     a.mtiles = a.B * tilesT * tilesH * tilesW;
     prof_name(IVF_CONV_HALO_BASE + V, "conv3d_halo_kernel<%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%s>", AM, t.TT, t.BN, t.WROWS, t.WCOLS,
               t.KS, t.BKH, t.TH, t.TW, t.TPS, t.DMA ? "true" : "false");
     const bool timed = prof_begin(s, IVF_CONV_HALO_BASE + V);
-    hipLaunchKernelGGL(kernel, dim3(a.mtiles * a.ntiles), dim3(NT), shm, s, a, tilesT, tilesH, tilesW);
+    hipLaunchKernelGGL(kernel, dim3(a.mtiles * a.ntiles), dim3(NT), shm, s, a, tilesT, tilesH, tilesW, short_edges);
     if (timed) prof_end(s);
     IVF_CHECK_LAUNCH();
     return IVF_OK;
