@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import arena_fill as AF
 import clstm_refs as CR
 from conftest import note
 
@@ -90,4 +91,15 @@ def test_clstm_case_matches_fp64_reference(cid):
         solo = _gpu_run(eng, case, bundle["x"][r:r + 1], bundle["targets"][r:r + 1], None)
         assert np.all(np.isfinite(solo["dx"]))
         failures += _check(case, bundle, solo, f"clip {r} alone", [r])
+    if cid == "S1":
+        # the same gate on a plan whose arenas held 0xFF (NaN) when it was bound and loaded and whose workspace holds
+        # it again before the forward: S1's unpool has to write the zeros of the dropped row itself
+        # (test_gpu_arena_contents.py has the matrix)
+        with AF.filled(0xFF):
+            ff = _engine(case)
+            ff.load_state_dict(bundle["sd"])
+            AF.refill(ff, 0xFF)
+            res = _gpu_run(ff, case, bundle["x"], bundle["targets"], bundle["dout"])
+        assert np.all(np.isfinite(res["dx"])), "dx has elements the backward never wrote"
+        failures += _check(case, bundle, res, f"b={case.b}/B={case.B} on 0xFF arenas", list(range(case.b)))
     assert not failures, "; ".join(failures)

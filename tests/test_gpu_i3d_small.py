@@ -5,6 +5,7 @@ backward on the gradient buffer and the activations (ReLU gates, arg-max inputs)
 flips and no tie ambiguity, every element of every buffer of all three clips is compared against its own gate, and
 pools and the layout conversions at both ends are compared bit for bit.  The gates come from the CPU floors of
 i3d_refs.reference (test_i3d_refs_host.py); nothing here is fitted to what the GPU gives."""
+import contextlib
 import time
 from collections import OrderedDict
 
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import arena_fill as AF
 import i3d_refs as R
 from conftest import note
 
@@ -21,15 +23,18 @@ _T0 = []
 _ENGINES = {}
 
 
-def engine(cid, mode, tuned=False):
-    """One engine per (case, mode[, tuned]) for the whole module, built-in kernel choice unless tuned."""
+def engine(cid, mode, tuned=False, fill=None):
+    """One engine per (case, mode[, tuned]) for the whole module, built-in kernel choice unless tuned.  fill: a byte
+    pattern (tests/arena_fill.py) both arenas hold when the plan is bound and its weights are loaded."""
     import ivf_engine
-    key = (cid, mode, tuned)
+    key = (cid, mode, tuned, fill)
     _T0.append(time.time())
     if key not in _ENGINES:
         case = R.CASES[cid]
-        eng = ivf_engine.I3DEngine(R.NUM_CLASSES, case.clip, max_batch=R.MAX_BATCH, softmax=True, math=mode, **case.engine)
-        eng.load_state_dict(R.state_dict(case), autotune=False)
+        with AF.filled(fill, outputs=False) if fill is not None else contextlib.nullcontext():
+            eng = ivf_engine.I3DEngine(R.NUM_CLASSES, case.clip, max_batch=R.MAX_BATCH, softmax=True, math=mode,
+                                       **case.engine)
+            eng.load_state_dict(R.state_dict(case), autotune=False)
         if tuned:
             eng.autotune(reps=1)
         eng.case_id = cid
@@ -64,12 +69,15 @@ def compare(results, bufs, extra, mode, gates, what):
     return worst, at
 
 
-def opwise(eng, cid, mode, variant, what, b=R.MAX_BATCH):
-    """forward at b clips, backward with a dense dout or the arg-max targets; every buffer of every clip."""
+def opwise(eng, cid, mode, variant, what, b=R.MAX_BATCH, fill=None):
+    """forward at b clips, backward with a dense dout or the arg-max targets; every buffer of every clip.  fill: the
+    byte pattern the whole workspace is set to before the forward."""
     case = R.CASES[cid]
     gates = R.reference(case, mode)["gate"]
     x = R.clips(case)[:b]
     xd = x.cuda()
+    if fill is not None:
+        AF.refill(eng, fill)
     probs, logits = eng.forward(xd, want_logits=True)
     acts = read_all(eng, b)
     assert bool((acts["input"][:, case.clip[0]:] == 0).all()), "pad channels of the cl4 input buffer"
@@ -100,6 +108,14 @@ def test_every_op_against_its_gate(plain, variant):
     cid, mode, eng = plain
     wf, af, wb, ab = opwise(eng, cid, mode, variant, f"{cid} {mode}")
     note(f"i3d small {cid} {mode} {variant}: worst measured/gate forward {wf:.3f} at {af}, backward {wb:.3f} at {ab}")
+    if cid == "gray":
+        # the same gates on a plan whose arenas held 0xFF (NaN in every float format of the plan) when it was bound and
+        # loaded, and whose workspace holds it again before the forward: test_gpu_arena_contents.py has the matrix
+        ff = engine(cid, mode, fill=0xFF)
+        with AF.filled(0xFF):
+            wf, af, wb, ab = opwise(ff, cid, mode, variant, f"{cid} {mode} 0xFF arenas", fill=0xFF)
+        note(f"i3d small {cid} {mode} {variant} on 0xFF arenas: worst measured/gate forward {wf:.3f} at {af}, "
+             f"backward {wb:.3f} at {ab}")
 
 
 # ------------------------------------------------------------------------------------------------ partial batch, rows
